@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- decoded symbols/sec of the ViterbiNet 'val' hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of VNETDetector.forward(y,'val') + on-device error counting over this rank's batch of
 synthetic words (BASELINE.json configs[1]: ViterbiNet L=4, 10 000 blocks x 1000 symbols per GPU, inputs
 resident in HBM).  Blocks are independent: every rank owns its own 10 000 blocks (weak scaling) and the only
 collective is one all-reduce of the int64[4] error counters at the end.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the line
+used to carry (sustained rate, FER curve, strong scaling, rooflines, the other BASELINE configs, CPU baselines).
+--dump-outputs DIR writes what the last timed step returned on rank 0 (decisions, error counters) as .npy files.
 """
 import argparse
 import ctypes
@@ -67,6 +71,29 @@ def profiled(path, kernel, field, workload):
         return t[kernel][field], f"profiles/{path} (offline rocprofv3 --pmc passes on this command, csrc {t['csrc_sha16']})"
     except (OSError, KeyError, ValueError):
         return None, f"profiles/{path}: no entry for {kernel}"
+
+
+DUMP_BYTES_MAX = 64_000_000
+
+
+def dump_outputs(out_dir, dec, counters):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as .npy files.  decisions.npy = float32
+    [B, T] bits of VNETDetector.forward(y,'val'); error_counters.npy = float64 [4] of count_errors' int64 counters, which
+    the steps accumulate (so: summed over the timed steps and, at N > 1, all-reduced over the ranks).  Decisions larger than
+    the 64 MB budget are written as a fixed, seeded sample of rows whose indices go to decision_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows_path = os.path.join(out_dir, "decision_rows.npy")
+    n_rows, row_bytes = dec.shape[0], dec.shape[1] * 4
+    budget = DUMP_BYTES_MAX - 4096  # (room for the counters and the .npy headers)
+    if n_rows * row_bytes > budget:
+        keep = budget // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+        np.save(rows_path, rows.astype(np.float64))
+        dec = dec[torch.from_numpy(rows).to(dec.device)]
+    elif os.path.exists(rows_path):
+        os.remove(rows_path)  # (left by an earlier sampled dump into the same folder)
+    np.save(os.path.join(out_dir, "decisions.npy"), dec.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "error_counters.npy"), counters.cpu().numpy().astype(np.float64))
 
 
 def event_time_ms(fn, iters, stream_device):
@@ -514,6 +541,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--blocks", type=int, default=10000, help="blocks per GPU (BASELINE configs[1]: 10000)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's decisions and error counters (rank 0) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything outside the headline: sustained rate, FER curve, strong scaling, rooflines, "
+                         "the other BASELINE configs, CPU baselines (the --no-* / --skip-* options below trim a --full run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 2 s sustained-rate loop")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling entry (the same 10 000 blocks split over the ranks)")
@@ -521,6 +553,8 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the per-config entries (BASELINE configs[0],[2],[3],[4])")
     ap.add_argument("--skip-fused-count", action="store_true", help="(profiling) keep every fused-kernel dispatch decode-only: no fused-count timing, no FER curve, no by-word configs")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -568,6 +602,7 @@ def main():
     def step():
         dec = det(y, "val", SNR_DB, GAMMA)
         mvn.count_errors(dec, tx, None, counters)
+        return dec
 
     # The GPU's clock / power state settles over ~30 ms of sustained load (tools/time_ramp.py: the first 20 launches of the
     # fused kernel run 1.52 ms, every later one 1.37): bring the device to its sustained state first, so that the W warm-up
@@ -586,8 +621,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    dec_last = step()  # (for --dump-outputs; the steps before it drop their decisions at once: one buffer, reused by every step)
     if world > 1:
         all_reduce(counters)  # the single collective: int64[4] error counters over RCCL/xGMI
     torch.cuda.synchronize(dev)
@@ -601,6 +637,9 @@ def main():
         elapsed = float(te.item())
 
     ser, fer = mvn.rates_from_counters(counters)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dec_last, counters)
+    del dec_last
     # what every rank decoded inside the timed region, gathered so that the line shows N ranks took part (and `value` is
     # their sum over the max-over-ranks time); the counters' frame count says the same through the all-reduce
     mine = torch.tensor([B * T * args.steps], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
@@ -620,7 +659,7 @@ def main():
 
     # sustained rate: the same step() for >= 2 s (the timed region above is tens of milliseconds), outside `value`
     sustained = None
-    if rank == 0 and not args.no_sustained:
+    if rank == 0 and args.full and not args.no_sustained:
         n_sus, t_sus = 0, time.perf_counter()
         while time.perf_counter() - t_sus < args.sustained_seconds:
             for _ in range(20):
@@ -636,7 +675,7 @@ def main():
     # FER@SNR / SER@SNR curve (the second half of BASELINE's metric), outside the timed region: fresh words per SNR
     # point on every rank, fused decode+count, one all-reduce of the int64[4] counters per point.
     fer_curve = []
-    for snr_db in (() if args.skip_fused_count else (7.0, 8.0, 9.0, 10.0, 11.0, 12.0)):  # plotter_main.py:117-122: 7..12 dB
+    for snr_db in ((7.0, 8.0, 9.0, 10.0, 11.0, 12.0) if args.full and not args.skip_fused_count else ()):  # plotter_main.py:117-122: 7..12 dB
         txs, ys = mvn.synthetic_words(B, T, L, snr_db, GAMMA, dev, seed=7860002 + 100 * int(snr_db) + rank)
         c = det.val_count(ys, txs)
         if world > 1:
@@ -648,7 +687,7 @@ def main():
     # ---- strong scaling of the same workload: BASELINE configs[1]'s 10 000 blocks SPLIT over the ranks (the reference calls the
     # detector with whatever its evaluation holds, trainer.py:232), next to the weak-scaling headline above.  Outside `value`.
     strong = None
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         lo_s, hi_s = mvn.shard_range(args.blocks, rank, world)
         ys, txs_ = y[lo_s:hi_s], tx[lo_s:hi_s]  # (rank r's share of ITS 10 000 words: same distribution on every rank)
         cs = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -689,6 +728,28 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "decoded symbols/sec, ViterbiNet L=4 ISI (16 states)",
+            "value": total_symbols / elapsed,
+            "unit": "symbols/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": f"ViterbiNet L=4, {B} blocks x {T} symbols per GPU (BASELINE configs[1])",
+                       "blocks_per_gpu": B, "block_length": T, "n_states": S, "snr_db": SNR_DB,
+                       "weights": "tests/golden/g7_by_word.npz (trained on the reference)",
+                       "parallelism": f"block-sharded x{world}, one all-reduce of int64[4] counters"},
+            "collective": collective,
+            "ser_at_snr": ser,
+            "fer_at_snr": fer,
+        }
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, timed alone with HIP events on its launch stream
         lib = mvn._lib.load()
         st = mvn._lib.current_stream(dev)
@@ -712,27 +773,8 @@ def main():
         # (rocprofv3 names the kernel without the launcher's " rings of N" suffix)
         traffic_fused, traffic_fused_src = profiled("traffic.json", fused_kernel.split(" rings of")[0], "bytes_per_launch", (B, T, S))
         traffic_acs, traffic_acs_src = profiled("traffic.json", acs_kernel, "bytes_per_launch", (B, T, S))
-        out = {
-            "metric": "decoded symbols/sec, ViterbiNet L=4 ISI (16 states)",
-            "value": total_symbols / elapsed,
-            "unit": "symbols/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"ViterbiNet L=4, {B} blocks x {T} symbols per GPU (BASELINE configs[1])",
-                       "blocks_per_gpu": B, "block_length": T, "n_states": S, "snr_db": SNR_DB,
-                       "weights": "tests/golden/g7_by_word.npz (trained on the reference)",
-                       "parallelism": f"block-sharded x{world}, one all-reduce of int64[4] counters"},
-            "collective": collective,
+        out.update({
             "sustained": sustained,
-            "ser_at_snr": ser,
-            "fer_at_snr": fer,
             "fer_curve": fer_curve,
             "roofline": {"kernel": fused_kernel + " (ViterbiNet MLP on f32 MFMA 16x16x4, in-place DPP trellis sweep)", "bound": "mfma",
                          "achieved": mlp_tflops, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -751,11 +793,12 @@ def main():
             "fused_decode_count": {"what": "mvn_vnet_decode_count_f32: decode + error counting in one launch, no decision "
                                            "store (4 B/symbol of HBM traffic); same counters as `value`'s two-launch step",
                                    "ms_per_step": ms_fused_count, "symbols_per_s": B * T / (ms_fused_count * 1e-3)},
-        }
-    # the other BASELINE configs: after the headline kernels were timed (the by-word configs are latency-bound and let the
-    # clocks drop), every rank takes part
-    configs = [] if args.no_configs else run_configs(dev, rank, world, all_reduce, backend, weights, by_word=not args.skip_fused_count)
-    if rank == 0:
+        })
+    if args.full:
+        # the other BASELINE configs: after the headline kernels were timed (the by-word configs are latency-bound and let the
+        # clocks drop), every rank takes part
+        configs = [] if args.no_configs else run_configs(dev, rank, world, all_reduce, backend, weights, by_word=not args.skip_fused_count)
+    if rank == 0 and args.full:
         out["configs"] = configs
         if sustained is not None:
             sustained["ratio_to_value"] = sustained["symbols_per_s"] * world / out["value"]  # per-GPU sustained rate x N vs the timed region
@@ -767,6 +810,7 @@ def main():
         else:
             out["cpu_baseline"] = {"value": None, "unit": "symbols/s", "cores": None, "kind": "port",
                                    "sample": "timed at N=1 only (the other ranks would wait for it); see the N=1 line"}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -86,6 +86,29 @@ def test_bench_self_launch_two_ranks():
     _check_collective_fields(out, 2, 512, 2)
 
 
+@pytest.mark.timeout(300)
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline fields only (the rest is --full's) and --dump-outputs writes what the last
+    timed step returned: the [B, T] decisions as float32 bits and the accumulated int64[4] counters as float64."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--blocks", "512", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=260)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["unit"] == "symbols/s" and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert out["value"] == pytest.approx(512 * 1000 * 3 / (out["ms_per_step"] * 1e-3 * 3), rel=1e-6)
+    assert not {"configs", "sustained", "fer_curve", "strong_scaling", "roofline", "cpu_baseline"} & set(out)
+    dec = np.load(tmp_path / "decisions.npy")
+    c = np.load(tmp_path / "error_counters.npy")
+    assert dec.dtype == np.float32 and dec.shape == (512, 1000) and set(np.unique(dec)) <= {0.0, 1.0}
+    assert c.dtype == np.float64 and c.shape == (4,)
+    assert c[1] == 3 * 512 * 1000 and c[3] == 3 * 512  # symbols and frames of the three timed steps
+    assert (out["ser_at_snr"], out["fer_at_snr"]) == pytest.approx((c[0] / c[1], c[2] / c[3]), rel=1e-6)
+    assert not (tmp_path / "decision_rows.npy").exists()  # 2 MB of decisions: written whole, not sampled
+
+
 def _check_collective_fields(out, world, blocks, steps):
     """The fields that let a reader of the JSON line confirm that N ranks took part in the collective."""
     c = out["collective"]
@@ -104,7 +127,7 @@ def test_bench_self_launch_four_ranks_with_configs():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(MVN_BENCH_BACKEND="gloo", MVN_BENCH_TRIALS_SELFSUP="6", MVN_BENCH_TRIALS_META="3", MVN_BENCH_TRIALS_META_MORE="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--blocks", "512", "--sustained-seconds", "0.2"], env=env, capture_output=True, text=True, timeout=860)
+                        "--blocks", "512", "--sustained-seconds", "0.2", "--full"], env=env, capture_output=True, text=True, timeout=860)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -230,3 +230,24 @@ def test_trial_draws_and_descriptor_helpers():
     assert trials.TRIAL_DTYPE.itemsize == 232
     # the reference's per-block ser from an error count (metrics.py:11-16), vectorised
     assert mvn.metrics.ser_from_errors(np.array([0, 3, 120]), 120).tolist() == [0.0, 1.0 - float(np.float32(117) / np.float32(120)), 1.0]
+
+
+def test_bench_dump_outputs_samples_rows_over_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs keeps its files under the byte budget: decisions that do not fit are written as a fixed,
+    seeded sample of rows (the same rows every run) with their indices beside them; a batch that fits is written whole."""
+    import bench
+
+    dec = torch.arange(40 * 10, dtype=torch.float32).reshape(40, 10)
+    counters = torch.tensor([3, 400, 1, 40], dtype=torch.int64)
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4096 + 10 * 4 * 40 - 1)  # one row short of the whole batch
+    bench.dump_outputs(str(tmp_path), dec, counters)
+    rows = np.load(tmp_path / "decision_rows.npy")
+    got = np.load(tmp_path / "decisions.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 40 and np.all(np.diff(rows) > 0)
+    assert got.dtype == np.float32 and np.array_equal(got, dec.numpy()[rows.astype(np.int64)])
+    assert np.load(tmp_path / "error_counters.npy").tolist() == [3.0, 400.0, 1.0, 40.0]
+    bench.dump_outputs(str(tmp_path / "again"), dec, counters)
+    assert np.array_equal(np.load(tmp_path / "again" / "decision_rows.npy"), rows)
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 64_000_000)
+    bench.dump_outputs(str(tmp_path), dec, counters)
+    assert np.array_equal(np.load(tmp_path / "decisions.npy"), dec.numpy()) and not (tmp_path / "decision_rows.npy").exists()

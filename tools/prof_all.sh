@@ -24,13 +24,13 @@ bash tools/pmc_sq.sh gpurun_out/r05p/pmc_va256 tools/prof_va256.py 125000 3 > $O
 python3 tools/pmc_dispatch_table.py gpurun_out/r05p/pmc_va256 va256_wave | (read h; echo "$h"; tail -3) > $O/va256_pmc.csv
 echo pmc headline + va256 done
 cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 echo bench done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o t -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-sustained > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o t -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-sustained > /dev/null 2>&1
 python3 $R/tools/stats_by_grid.py $O/kt/t_kernel_trace.csv > $O/kernel_durations_by_grid.csv
 cp $O/kt/t_kernel_stats.csv $O/kernel_stats.csv
 echo kt done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kh -o t -- python3 $R/bench.py --no-cpu-baseline --no-configs --skip-fused-count --no-sustained > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kh -o t -- python3 $R/bench.py --full --no-cpu-baseline --no-configs --skip-fused-count --no-sustained > /dev/null 2>&1
 cp $O/kh/t_kernel_stats.csv $O/headline_kernel_stats.csv
 python3 $R/tools/stats_by_grid.py $O/kh/t_kernel_trace.csv > $O/headline_by_grid.csv
 echo kh done
