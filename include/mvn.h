@@ -43,7 +43,7 @@ extern "C" {
 typedef void *mvn_stream_t; /* hipStream_t */
 
 #define MVN_OK 0
-#define MVN_E_DIMS (-1)      /* negative size, T > ld, ... */
+#define MVN_E_DIMS (-1)      /* negative size, T > ld, a non-Adam optimizer tag for the meta-learning calls, ... */
 #define MVN_E_STATES (-2)    /* S not a power of two in [2,256] */
 #define MVN_E_PRIORS (-3)    /* Bp < 1 or B % Bp != 0 */
 #define MVN_E_NULL (-4)      /* required pointer is NULL */
@@ -222,7 +222,7 @@ int mvn_count_errors(const float *dec, int64_t dec_ld, const float *tx, int64_t 
  * The trainer's other optimizers (deep_learning_setup, trainer.py:163-175) ride on the same arguments: beta1 = MVN_BETA1_RMSPROP
  * runs torch.optim.RMSprop's update (alpha = beta2, eps; square average in adam_v, adam_m untouched; torch's defaults: no
  * momentum, not centered), beta1 = MVN_BETA1_SGD torch.optim.SGD's (p -= lr g; adam_m / adam_v untouched).  The same holds for
- * the _ws_ and _trials_ forms of this call; the meta-learning calls below take Adam only.
+ * the _ws_ and _trials_ forms of this call; the meta-learning calls below take Adam only and return MVN_E_DIMS for beta1 < 0.
  */
 #define MVN_BETA1_RMSPROP (-1.0f)
 #define MVN_BETA1_SGD (-2.0f)

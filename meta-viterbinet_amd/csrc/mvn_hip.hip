@@ -1493,7 +1493,8 @@ int mvn_vnet_maml_train_ws_f32(const float *rx_words, const int32_t *labels, int
                                float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0, float meta_lr,
                                int32_t second_order, float lr, float beta1, float beta2, float eps, float *loss_out, int32_t S,
                                void *workspace, size_t workspace_bytes, int32_t *status, mvn_stream_t stream) {
-    if (T < 1 || W < 1 || n_steps < 0 || step0 < 0) return MVN_E_DIMS;
+    // Adam only: the RMSprop / SGD tags (beta1 < 0) would turn lr / (1 - beta1^t) into an infinite or wrong step size
+    if (T < 1 || W < 1 || n_steps < 0 || step0 < 0 || beta1 < 0.0f) return MVN_E_DIMS;
     if (!valid_states(S) || S > 32) return MVN_E_STATES;  // four parameter-sized vectors + a chunk must fit the 160-KB LDS
     if (n_steps == 0) return MVN_OK;
     if (!rx_words || !labels || !support_idx || !query_idx || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !adam_m || !adam_v)
@@ -1522,7 +1523,7 @@ int mvn_vnet_maml_train_ws_f32(const float *rx_words, const int32_t *labels, int
 int mvn_vnet_maml_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t W, float meta_lr,
                                    int32_t second_order, float lr, float beta1, float beta2, float eps, int32_t S,
                                    void *workspace, size_t workspace_bytes, mvn_stream_t stream) {
-    if (T < 1 || W < 1 || R < 0) return MVN_E_DIMS;
+    if (T < 1 || W < 1 || R < 0 || beta1 < 0.0f) return MVN_E_DIMS;  // (Adam only, as above)
     if (!valid_states(S) || S > 32) return MVN_E_STATES;
     if (R == 0) return MVN_OK;
     if (!trials) return MVN_E_NULL;

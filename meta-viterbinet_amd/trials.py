@@ -17,6 +17,7 @@ ser_by_word, final weights, Adam moments -- are bit-identical to harness.eval_by
 (tests/test_gpu_trials.py::test_batched_trials_equal_sequential_runs).
 """
 import ctypes
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -38,16 +39,29 @@ def param_offsets(n_states: int) -> np.ndarray:
     return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
 
 
+def _pow(b: float, s: int) -> float:
+    """libm's pow(b, s) for a double b and an integer s >= 0.  Python's float ** int is that pow, except that it raises
+    OverflowError where pow returns an infinity (|b| > 1 and a large s: SGD's tag beta1 = -2 from step 1024 on)."""
+    try:
+        return b ** s
+    except OverflowError:
+        return -math.inf if b < 0 and s % 2 else math.inf
+
+
 def beta_power(beta: float, step: int) -> float:
-    """(double)(float)beta ** step, exactly what the single-trial C entry points compute from (beta, step0)."""
-    return float(np.float32(beta)) ** int(step)
+    """(double)(float)beta ** step, exactly what the single-trial C entry points compute from (beta, step0): C's pow, bit for
+    bit, for every float beta and step >= 0 (+-inf on overflow, 0 on underflow)."""
+    return _pow(float(np.float32(beta)), int(step))
 
 
 def beta_powers(beta: float, steps) -> np.ndarray:
     """beta_power for an array of step counts, one libm pow() each (a vectorised pow may round differently: the batched run
     must hand its kernels the very doubles the single-trial entry points compute)."""
     b = float(np.float32(beta))
-    return np.array([b ** int(s) for s in steps], dtype=np.float64)
+    try:  # (the loop of every call that does not overflow: Adam's and RMSprop's powers never do)
+        return np.array([b ** int(s) for s in steps], dtype=np.float64)
+    except OverflowError:
+        return np.array([_pow(b, int(s)) for s in steps], dtype=np.float64)
 
 
 class TrialDraws:

@@ -89,6 +89,17 @@ def test_argument_validation_needs_no_device(lib):
     assert lib.mvn_vnet_online_train_trials_f32(None, 4, 136, 0, 1e-3, 0.9, 0.999, 1e-8, 16, None, 0, None) == -4
     assert lib.mvn_vnet_maml_train_trials_f32(None, 4, 136, 0, 0.1, 1, 1e-3, 0.9, 0.999, 1e-8, 16, None, 0, None) == -1
     assert lib.mvn_vnet_maml_train_trials_f32(None, 4, 136, 1, 0.1, 1, 1e-3, 0.9, 0.999, 1e-8, 16, None, 0, None) == -4
+    # the meta-learning calls take Adam only: the RMSprop / SGD tags (include/mvn.h) are rejected before any pointer is looked at,
+    # the online-training calls take both
+    maml = lambda fn, beta1, *ws: fn(None, None, 136, None, 1, None, 2, *([None] * 8), 0, 0.1, 1, 1e-3, beta1, 0.999,  # noqa: E731
+                                     1e-8, None, 16, *ws, None)
+    for beta1, beta2, eps, rc in ((-1.0, 0.99, 1e-8, -1), (-2.0, 0.0, 0.0, -1), (0.9, 0.999, 1e-8, -4)):  # MVN_BETA1_RMSPROP, _SGD, Adam
+        assert maml(lib.mvn_vnet_maml_train_f32, beta1) == rc, beta1
+        assert maml(lib.mvn_vnet_maml_train_ws_f32, beta1, None, 0, None) == rc, beta1
+        assert lib.mvn_vnet_maml_train_trials_f32(None, 4, 136, 1, 0.1, 1, 1e-3, beta1, beta2, eps, 16, None, 0, None) == rc, beta1
+        assert lib.mvn_vnet_online_train_trials_f32(None, 4, 136, 0, 1e-3, beta1, beta2, eps, 16, None, 0, None) == -4, beta1
+        assert lib.mvn_vnet_online_train_f32(None, None, 136, None, 0, 2, *([None] * 8), 0, 1e-3, beta1, beta2, eps, None, 16,
+                                             None) == -4, beta1
     one = lib.mvn_vnet_train_trials_workspace_bytes(16, 136, 1, 1)
     assert one > 0 and one % 256 == 0 and lib.mvn_vnet_train_trials_workspace_bytes(16, 136, 1, 7) == 7 * one
     assert lib.mvn_vnet_train_trials_workspace_bytes(16, 32, 1, 4) == lib.mvn_vnet_train_trials_workspace_bytes(16, 32, 1, 1) * 4

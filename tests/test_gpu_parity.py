@@ -777,18 +777,27 @@ def test_reference_word_stream_replays_the_dataset(golden, dev, name):
 
 
 # ---------------------------------------------------------------- next #3: online (self-supervised) training in one launch
-def _torch_online_ref(w, y, labels, idx, lr, n_iter, full_word=False, optimizer="Adam"):
+def _torch_online_ref(w, y, labels, idx, lr, n_iter, full_word=False, optimizer="Adam", state=None, dtype=torch.float32):
     """The reference's arithmetic for run_train_loop (trainer.py:492-505): torch autograd, CrossEntropyLoss(mean),
-    torch.optim.Adam, on CPU in fp32.  (A torch reference is the right oracle for this floating-point kernel.)"""
+    torch.optim.Adam, on CPU in fp32.  (A torch reference is the right oracle for this floating-point kernel.)
+    state: the optimizer's starting state, flat [P] arrays in parameters() order and the steps already taken -- Adam
+    {step, exp_avg, exp_avg_sq}, RMSprop {step, square_avg}, SGD none -- updated in place to the end state.
+    dtype=torch.float64 makes it a high-precision referee (weights, word and optimizer state in double)."""
     net = torch.nn.Sequential(torch.nn.Linear(1, 100), torch.nn.Sigmoid(), torch.nn.Linear(100, 50), torch.nn.ReLU(),
-                              torch.nn.Linear(50, w[4].shape[0]))
+                              torch.nn.Linear(50, w[4].shape[0])).to(dtype)
     with torch.no_grad():
         for p, a in zip(net.parameters(), w):
             p.copy_(torch.tensor(a))
     opt = getattr(torch.optim, optimizer)(net.parameters(), lr=lr)  # (deep_learning_setup, trainer.py:163-175: torch's defaults)
+    moments = [k for k in ("exp_avg", "exp_avg_sq", "square_avg") if state is not None and k in state]
+    off = np.cumsum([0] + [p.numel() for p in net.parameters()])
+    if state is not None and optimizer != "SGD":  # (torch.optim.SGD without momentum keeps no state)
+        for i, p in enumerate(net.parameters()):
+            opt.state[p] = {"step": torch.tensor(float(state["step"]), dtype=torch.float64),
+                            **{k: torch.tensor(state[k][off[i]:off[i + 1]], dtype=dtype).reshape(p.shape) for k in moments}}
     crit = torch.nn.CrossEntropyLoss()
     losses = []
-    yt, lt = torch.tensor(y).reshape(-1, 1), torch.tensor(labels).long()
+    yt, lt = torch.tensor(y).to(dtype).reshape(-1, 1), torch.tensor(labels).long()
     for it in range(n_iter):
         logits = net(yt)
         loss = crit(logits, lt) if full_word else crit(logits[torch.tensor(idx[it]).long()], lt[torch.tensor(idx[it]).long()])
@@ -797,6 +806,11 @@ def _torch_online_ref(w, y, labels, idx, lr, n_iter, full_word=False, optimizer=
         loss.backward()
         opt.step()
         losses.append(float(loss))
+    if state is not None:
+        state["step"] = int(state["step"]) + n_iter
+        if optimizer != "SGD":
+            for k in moments:
+                state[k] = np.concatenate([opt.state[p][k].reshape(-1).numpy() for p in net.parameters()])
     return [p.detach().numpy() for p in net.parameters()], np.array(losses)
 
 
@@ -977,6 +991,127 @@ def test_online_training_other_optimizers_vs_torch(dev, monkeypatch, optimizer, 
     assert moved > 1e-4
     for i in range(6):
         assert np.all(np.abs(got[i] - ref_w[i]) <= 2e-5 + 1e-3 * np.abs(ref_w[i])), i
+
+
+# Starting step counts of the online-training test below, each for two calls of two iterations: across 1024 (SGD's tag gives
+# beta1^t = (-2)^t = +inf from t = 1024 on: the second call starts there), from an odd step above it (-inf), and far out
+# (Adam's bias corrections exactly 1)
+LARGE_STEP0 = {"across_1024": 1022, "odd_above_1024": 1025, "huge": 100000}
+# (S, form): the online-training launcher's forms -- S = 16 on one workgroup (minibatch iterations, MVN_TRAIN_GROUPS=0), one
+# workgroup per 32-sample chunk (whole word, MVN_TRAIN_GROUPS=1) and the trial-batched entry point (minibatch, two trials);
+# S = 64 / 128 on online_train_kernel<64|128>, the moments in global memory
+LARGE_STEP_FORMS = [(16, "one"), (16, "chunked"), (16, "trials"), (64, "one"), (128, "one")]
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("boundary", sorted(LARGE_STEP0))
+@pytest.mark.parametrize("S,form", LARGE_STEP_FORMS)
+@pytest.mark.parametrize("optimizer", ["Adam", "RMSprop", "SGD"])
+def test_online_training_from_large_step_counts_vs_float64_torch(dev, monkeypatch, optimizer, S, form, boundary):
+    """The online-training kernels with an optimizer that has already taken 1022 / 1025 / 100000 steps and holds a non-trivial
+    state, against torch autograd + torch.optim in float64 started from the same state, carried over two calls.  The kernels
+    receive beta1^step0 and beta2^step0 as doubles: for Adam the bias corrections (1 - 0.999^1023 = 0.64), for RMSprop / SGD
+    their tags' powers, +-1 and +-inf, which must leave the plain learning rate alone.  The trial-batched form gets them from
+    trials.beta_powers of TrialBank.step, as the lock-step engine fills its descriptors.  Tolerances as against fp32 torch."""
+    from meta_viterbinet_amd import trials as tr_mod
+
+    T, L = 136, {16: 4, 64: 6, 128: 7}[S]
+    full_word = form == "chunked" or S == 128
+    step0 = LARGE_STEP0[boundary]
+    rng = np.random.RandomState(S + step0 % 1000 + len(optimizer))
+    w = _rand_weights(S, rng)
+    P = sum(a.size for a in w)
+    tx = rng.randint(0, 2, (1, T)).astype(np.float32)
+    y = rng.normal(0, 1.5, (1, T)).astype(np.float32)
+    labels = mvn.calculate_states(L, torch.tensor(tx)).numpy()
+    n_iter, n1 = 4, 2
+    idx = np.stack([rng.choice(np.arange(1, T), 32, replace=False) for _ in range(n_iter)]).astype(np.int32)
+    m0 = (0.01 * rng.standard_normal(P)).astype(np.float32)  # a state like one after many steps: both moments non-zero
+    v0 = rng.uniform(1e-5, 1e-3, P).astype(np.float32)
+    lr = 0.05 if optimizer == "SGD" else 1e-3
+    state = {"Adam": {"exp_avg": m0, "exp_avg_sq": v0}, "RMSprop": {"square_avg": v0}, "SGD": {}}[optimizer]
+    state = {"step": step0, **{k: a.astype(np.float64) for k, a in state.items()}}
+    ref_w, ref_loss = _torch_online_ref(w, y[0], labels, idx, lr, n_iter, full_word, optimizer, state, torch.float64)
+    assert state["step"] == step0 + n_iter
+    monkeypatch.setenv("MVN_TRAIN_GROUPS", "1" if form == "chunked" else "0")
+    lib = mvn._lib.load()
+    name = ctypes.create_string_buffer(128)
+    if form == "trials":
+        R = 2
+        bank = tr_mod.TrialBank([w] * R, S, L, dev, lr=lr, optimizer_type=optimizer)
+        bank.exp_avg.copy_(torch.tensor(m0, device=dev).expand(R, P))
+        bank.exp_avg_sq.copy_(torch.tensor(v0, device=dev).expand(R, P))
+        bank.step[:] = step0
+        yt = torch.tensor(y, device=dev).repeat(R, 1).contiguous()
+        lab = torch.tensor(labels, device=dev).to(torch.int32).reshape(1, T).repeat(R, 1).contiguous()
+        bidx = torch.tensor(idx, device=dev).unsqueeze(0).repeat(R, 1, 1).contiguous()
+        loss_d = torch.full((R, n_iter), np.nan, dtype=torch.float32, device=dev)
+        th = bank.pointers(bank.theta)
+        b1, b2, eps = {"Adam": (0.9, 0.999, 1e-8), "RMSprop": (-1.0, 0.99, 1e-8), "SGD": (-2.0, 0.0, 0.0)}[optimizer]
+        assert lib.mvn_vnet_train_kernel_name(0, R, T, 32, S, 0, name, 128) == 0
+        assert name.value.decode() == f"online_train_kernel<{S}, true> 1x{R}"
+        descs = []
+        for lo, n in ((0, n1), (n1, n_iter - n1)):
+            d = np.zeros(R, dtype=tr_mod.TRIAL_DTYPE)
+            d["y"] = [yt[r].data_ptr() for r in range(R)]
+            d["labels"] = [lab[r].data_ptr() for r in range(R)]
+            d["idx"] = [bidx[r, lo:].data_ptr() for r in range(R)]
+            d["w_in"], d["w_out"] = th, th
+            d["adam_m"] = [bank.exp_avg[r].data_ptr() for r in range(R)]
+            d["adam_v"] = [bank.exp_avg_sq[r].data_ptr() for r in range(R)]
+            d["loss_out"] = [loss_d[r, lo:].data_ptr() for r in range(R)]
+            d["b1pow"], d["b2pow"] = tr_mod.beta_powers(b1, bank.step), tr_mod.beta_powers(b2, bank.step)
+            d["n"] = n
+            bank.step += n
+            dd = torch.from_numpy(d.view(np.uint8)).to(dev)
+            descs.append(dd)  # (alive until the launch has run)
+            assert lib.mvn_vnet_online_train_trials_f32(mvn._lib.ptr(dd), R, T, 32, lr, b1, b2, eps, S, None, 0,
+                                                        mvn._lib.current_stream(dev)) == 0
+        torch.cuda.synchronize()
+        if optimizer == "SGD":  # beta1^step0 of the second call: +inf from 1024, -inf at odd steps above
+            assert np.isinf(d["b1pow"]).all()
+        assert torch.equal(bank.theta[0], bank.theta[1]) and torch.equal(bank.exp_avg_sq[0], bank.exp_avg_sq[1])
+        assert np.array_equal(bank.step, [step0 + n_iter] * R)
+        got, m, v, loss = [_np(t) for t in bank.weights(0)], _np(bank.exp_avg[0]), _np(bank.exp_avg_sq[0]), _np(loss_d[0])
+    else:
+        det = _vnet_with(w, S, T, dev)
+        tr = mvn.OnlineTrainer(det, L, lr=lr, optimizer_type=optimizer)
+        tr.exp_avg.copy_(torch.tensor(m0, device=dev))
+        tr.exp_avg_sq.copy_(torch.tensor(v0, device=dev))
+        tr.step = step0
+        ws = tr._workspace(S, dev).numel()
+        assert lib.mvn_vnet_train_kernel_name(0, 0, T, 0 if full_word else 32, S, ws, name, 128) == 0
+        want = f"online_train_groups_kernel<{S}, false> 5x1" if form == "chunked" else f"online_train_kernel<{S}, false> 1x1"
+        assert name.value.decode().startswith(want), name.value
+        txt, yt = torch.tensor(tx, device=dev), torch.tensor(y, device=dev)
+        losses = [tr.online_training(txt, yt, iterations=n, batch_idx=torch.tensor(idx[lo:lo + n], device=dev), full_word=full_word,
+                                     return_loss=True) for lo, n in ((0, n1), (n1, n_iter - n1))]
+        tr.check_status()
+        assert tr.step == step0 + n_iter
+        got, m, v, loss = [_np(p) for p in det.net.parameters()], _np(tr.exp_avg), _np(tr.exp_avg_sq), np.concatenate([_np(t) for t in losses])
+    for a in got + [m, v, loss]:
+        assert np.isfinite(a).all()
+    if optimizer == "SGD":
+        assert np.array_equal(m, m0) and np.array_equal(v, v0)  # torch.optim.SGD without momentum keeps no state
+    elif optimizer == "RMSprop":
+        assert np.array_equal(m, m0)  # the square average lives in exp_avg_sq; exp_avg is not RMSprop's
+        assert np.all(np.abs(v - state["square_avg"]) <= 1e-3 * np.abs(state["square_avg"])) and not np.array_equal(v, v0)
+    else:
+        assert np.all(np.abs(v - state["exp_avg_sq"]) <= 1e-3 * np.abs(state["exp_avg_sq"])) and not np.array_equal(v, v0)
+        assert np.all(np.abs(m - state["exp_avg"]) <= 1e-6 + 1e-3 * np.abs(state["exp_avg"])) and not np.array_equal(m, m0)
+    moved = max(float(np.abs(got[i] - w[i]).max()) for i in range(6))
+    worst = max(float(np.abs(got[i] - ref_w[i]).max()) for i in range(6))
+    # against the float64 referee the fp32 result is also within a few roundings of the weight plus 1e-3 of the update itself:
+    # a step size or bias correction off by 0.1 % fails here (the tolerance above allows 1e-3 of the weight)
+    tight = [2e-7 + 4 * np.spacing(np.abs(ref_w[i]).astype(np.float32)) + 1e-3 * np.abs(ref_w[i] - w[i]) for i in range(6)]
+    ratio = max(float((np.abs(got[i] - ref_w[i]) / tight[i]).max()) for i in range(6))
+    print(f"online training {optimizer} S={S} {form} from step {step0}: weights moved {moved:.2e}, {worst:.2e} from float64 torch "
+          f"({ratio:.2f} of the update tolerance)")
+    assert moved > 1e-4
+    assert np.allclose(loss, ref_loss, rtol=2e-4, atol=1e-6)
+    for i in range(6):
+        assert np.all(np.abs(got[i] - ref_w[i]) <= 2e-5 + 1e-3 * np.abs(ref_w[i])), i
+        assert np.all(np.abs(got[i] - ref_w[i]) <= tight[i]), i
 
 
 def test_online_training_draws_like_select_batch(dev):

@@ -346,6 +346,47 @@ def test_batched_evaluation_switches_equal_sequential_runs(golden, dev, flow):
 
 
 @pytest.mark.timeout(900)
+@pytest.mark.parametrize("cohorts", [1, 2])
+@pytest.mark.parametrize("opt,lr", [("RMSprop", 1e-3), ("SGD", 0.05)])
+def test_lock_step_engine_past_1024_optimizer_steps_equals_sequential_runs(golden, dev, monkeypatch, opt, lr, cohorts):
+    """RMSprop / SGD through the lock-step engine (no online meta-learning, 16 states) at the reference's training length:
+    200 self-supervised iterations on every block (ser_thresh = 1 buffers every word), so every trial's optimizer passes step
+    1024, where SGD's tag makes the descriptors' beta1^step = (-2)^step overflow to +-inf (the single-trial entry points get
+    the same from libm's pow).  Per trial identical to harness.eval_by_word with the same draws: ser_by_word, weights, both
+    moments, step counts; with one cohort and with two stepping alternately."""
+    from meta_viterbinet_amd import trials as tr_mod
+
+    def not_lock_step(*a, **k):
+        raise AssertionError("eval_by_word_batched left the lock-step engine")
+
+    monkeypatch.setattr(tr_mod, "_one_trial_at_a_time", not_lock_step)
+    kw = dict(self_supervised=True, self_supervised_iterations=200, online_meta=False, ser_thresh=1.0)
+    R, N, K, nsym, sub = 3, 11, 120, 2, 25
+    T = K + 8 * nsym
+    snrs = [7.0, 9.0, 11.0]
+    w = _trial_weights(golden, R, seed=13)
+    msg, rx = _words(dev, R, N, K, nsym, snrs, seed=41)
+    bank = TrialBank(w, 16, 4, dev, lr=lr, optimizer_type=opt)
+    rec = {}
+    ser_b = eval_by_word_batched(bank, msg, rx, nsym, sub, [TrialDraws(700 + r, dev) for r in range(R)], record=rec, cohorts=cohorts, **kw)
+    assert int(rec["trained"].sum(axis=1).min()) >= 7
+    assert int(bank.step.min()) > 1024, bank.step
+    print(f"lock-step {opt}, {cohorts} cohort(s): bank.step {bank.step.tolist()}")
+    assert torch.isfinite(bank.theta).all() and torch.isfinite(bank.exp_avg_sq).all()
+    for r in range(R):
+        det = _vnet_with(w[r], T, dev)
+        tr = mvn.OnlineTrainer(det, 4, lr=lr, optimizer_type=opt)
+        ser = mvn.eval_by_word(det, msg[r], rx[r], snrs[r], 0.2, nsym, sub, online_trainer=tr, draws=TrialDraws(700 + r, dev), **kw)
+        assert np.array_equal(ser, ser_b[r]), (opt, r)
+        for a, b in zip(det.parameters(), bank.weights(r)):
+            assert torch.equal(a.detach(), b), (opt, r)
+        assert torch.equal(tr.exp_avg, bank.exp_avg[r]) and torch.equal(tr.exp_avg_sq, bank.exp_avg_sq[r]), (opt, r)
+        assert tr.step == int(bank.step[r]), (opt, r)
+    assert float(bank.exp_avg.abs().max()) == 0.0  # neither optimizer keeps a first moment
+    assert (float(bank.exp_avg_sq.abs().max()) > 0.0) == (opt == "RMSprop")
+
+
+@pytest.mark.timeout(900)
 def test_many_trials_take_the_one_workgroup_per_trial_form_by_themselves(golden, dev, monkeypatch):
     """The launcher's OWN choice at the trial counts bench.py quotes (256 per GPU): from ~154 training trials on, one
     workgroup per trial -- online_train_kernel<16, true> on whole words and maml_train_kernel<16, true> -- instead of one per

@@ -232,6 +232,33 @@ def test_trial_draws_and_descriptor_helpers():
     assert mvn.metrics.ser_from_errors(np.array([0, 3, 120]), 120).tolist() == [0.0, 1.0 - float(np.float32(117) / np.float32(120)), 1.0]
 
 
+def test_descriptor_beta_powers_equal_libm_pow_past_1024_steps():
+    """The trial descriptors' b1pow / b2pow (trials.beta_power / beta_powers) against libm's pow((double)(float)beta, step) --
+    what the single-trial C entry points compute -- bit for bit, for every beta encoding the training kernels receive (Adam's
+    0.9 / 0.999, RMSprop's tag -1 and alpha 0.99, SGD's tag -2 and 0) at step counts a trial reaches with the reference's
+    200 iterations per block: SGD's (-2)^t overflows to +-inf from t = 1024 on (sign by parity), Adam's powers underflow to 0."""
+    import ctypes.util
+
+    from meta_viterbinet_amd import trials
+
+    libm = ctypes.CDLL(ctypes.util.find_library("m"))
+    libm.pow.restype, libm.pow.argtypes = ctypes.c_double, [ctypes.c_double, ctypes.c_double]
+    steps = [0, 1, 2, 1022, 1023, 1024, 1025, 1100, 45269, 10 ** 6]
+
+    def bits(x):
+        return np.asarray(x, dtype=np.float64).view(np.uint64)
+
+    for beta in (0.9, 0.999, -1.0, 0.99, -2.0, 0.0):
+        want = np.array([libm.pow(float(np.float32(beta)), float(s)) for s in steps])
+        got = trials.beta_powers(beta, np.array(steps, dtype=np.int64))
+        assert got.dtype == np.float64 and np.array_equal(bits(got), bits(want)), (beta, got, want)
+        for s, w in zip(steps, want):
+            assert bits(trials.beta_power(beta, s)) == bits(w), (beta, s)
+    # the edges themselves, so that the comparison above cannot pass on two equally wrong sides
+    assert trials.beta_powers(-2.0, [1023, 1024, 1025]).tolist() == [-(2.0 ** 1023), np.inf, -np.inf]
+    assert trials.beta_power(0.9, 10 ** 6) == 0.0 and trials.beta_power(0.0, 0) == 1.0 and trials.beta_power(-1.0, 45269) == -1.0
+
+
 def test_bench_dump_outputs_samples_rows_over_budget(tmp_path, monkeypatch):
     """bench.py --dump-outputs keeps its files under the byte budget: decisions that do not fit are written as a fixed,
     seeded sample of rows (the same rows every run) with their indices beside them; a batch that fits is written whole."""
