@@ -429,6 +429,30 @@ int mvn_rs_decode_bits_f32(const float *rx_bits, int64_t ld_in, float *msg_bits,
 int mvn_rs_encode_bits_f32(const float *msg_bits, int64_t ld_in, float *cw_bits, int64_t ld_out, int64_t B,
                            int32_t kbits, int32_t nsym, mvn_stream_t stream);
 
+/*
+ * LSTMDetector.forward(y,'val'), python_code/detectors/LSTM/lstm_detector.py:35-57, and MetaLSTMDetector.forward(y,'val',var),
+ * detectors/META_LSTM/meta_lstm_detector.py:23-70 (var = the ten arrays): the window x_t = [y[t-3], y[t-2], y[t-1], y[t]] (-100
+ * where the index is negative, :42-44), a unidirectional 2-layer LSTM (input 4, hidden 256, zero h and c per word, torch gate order
+ * i, f, g, o), Linear(256, 2) at every t, and torch.argmax over its two logits (the first index on a tie, a NaN counts as the
+ * maximum).  The sizes 4 / 256 / 2 layers / 2 classes are fixed.  Weights in torch layout, nn.LSTM.parameters() order then fc:
+ * W_ih0 [1024,4] W_hh0 [1024,256] b_ih0 b_hh0 [1024] W_ih1 [1024,256] W_hh1 [1024,256] b_ih1 b_hh1 [1024] fc_W [2,256] fc_b [2];
+ * read at call time, never cached.
+ *   y [B, y_ld>=T]; dec [B, dec_ld>=T] fp32 {0,1}; logits [B,T,2] contiguous or NULL;
+ *   workspace: mvn_lstm_workspace_bytes(B, T) bytes of device memory, 16-byte aligned (the weights repacked by the call; contents
+ *   irrelevant before and after, not to be shared by calls that may run concurrently).
+ * Arithmetic: every gate, and every logit, is one k-ordered fmaf chain (b_ih + b_hh, then W_ih . input, then W_hh . h; fc_b, then
+ * fc_W . h), sigmoid / tanh on SLEEF's expf (lstm.inc states the formulas): bit-identical to tests/native/lstm_twin.c, and the
+ * same bits for a word whatever B, its row, y_ld or the kernel form.  Returns MVN_E_DIMS for B < 0, T < 1 or a row stride < T,
+ * MVN_OK for B = 0, MVN_E_NULL for a missing pointer (logits may be NULL), MVN_E_WORKSPACE for a small or unaligned workspace.
+ * mvn_lstm_decode_kernel_name: the launches of the call for B words (one 16-word workgroup per tile; name is a host pointer).
+ */
+size_t mvn_lstm_workspace_bytes(int64_t B, int32_t T);
+int mvn_lstm_decode_f32(const float *y, int64_t y_ld, const float *W_ih0, const float *W_hh0, const float *b_ih0, const float *b_hh0,
+                        const float *W_ih1, const float *W_hh1, const float *b_ih1, const float *b_hh1, const float *fc_W,
+                        const float *fc_b, float *dec, int64_t dec_ld, float *logits, void *workspace, size_t workspace_bytes, int64_t B,
+                        int32_t T, mvn_stream_t stream);
+int mvn_lstm_decode_kernel_name(int64_t B, int32_t T, char *name, int32_t name_len);
+
 #ifdef __cplusplus
 }
 #endif

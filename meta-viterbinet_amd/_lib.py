@@ -66,6 +66,9 @@ SIGNATURES = {
     "mvn_rs_decode_bits_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     "mvn_rs_encode_bits_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
     "mvn_count_errors": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
+    "mvn_lstm_workspace_bytes": (ctypes.c_size_t, [_i64, _i32]),
+    "mvn_lstm_decode_f32": (ctypes.c_int, [_vp, _i64] + [_vp] * 10 + [_vp, _i64, _vp, _vp, ctypes.c_size_t, _i64, _i32, _vp]),
+    "mvn_lstm_decode_kernel_name": (ctypes.c_int, [_i64, _i32, ctypes.c_char_p, _i32]),
 }
 
 _lib = None

@@ -51,9 +51,9 @@ constexpr int kK3Steps = (kH2 + 3) / 4;  // 13 MFMA k-steps for layer 3 (k 50,51
 // Deterministic sigmoid: 1/(1+expf_u10(d)), d = -z.  Same operation sequence as
 // oracle/mvn_oracle.c:mvn_oracle_expf_u10 (SLEEF 1.0-ULP expf as ATen's vectorised sigmoid
 // evaluates it).  v_ldexp_f32 replaces SLEEF's two-step scaling: the two differ only when the
-// result is subnormal, and then 1+e == 1 either way.
+// result is subnormal, and then 1+e == 1 either way.  (expf_u10 alone: the LSTM's tanh, lstm.inc, which uses it only as 1 +- e.)
 // -------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sigmoid_from_neg(float d) {
+__device__ __forceinline__ float expf_u10(float d) {
     float dc = fminf(fmaxf(d, -128.0f), 128.0f);
     dc = d != d ? d : dc;  // NaN in -> NaN out, like the reference (the clamp alone would swallow it)
     float t = dc * 1.442695040888963407359924681001892137426645954152985934135449406931f;
@@ -68,8 +68,10 @@ __device__ __forceinline__ float sigmoid_from_neg(float d) {
     u = __builtin_fmaf(u, s, 0.166666671633720397949219f);
     u = __builtin_fmaf(u, s, 0.5f);
     u = 1.0f + __builtin_fmaf(s * s, u, s);
-    float e = ldexpf(u, q);
-    return 1.0f / (1.0f + e);  // IEEE division (hipcc default: correctly rounded)
+    return ldexpf(u, q);
+}
+__device__ __forceinline__ float sigmoid_from_neg(float d) {
+    return 1.0f / (1.0f + expf_u10(d));  // IEEE division (hipcc default: correctly rounded)
 }
 
 // va_detector.py:64-68, four separately rounded ops (three instructions: see below).
@@ -1141,6 +1143,8 @@ int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *man
     return MVN_OK;
 }
 
+#include "lstm.inc"
+
 }  // namespace
 
 // =============================================================================================
@@ -1727,6 +1731,32 @@ int mvn_count_errors(const float *dec, int64_t dec_ld, const float *tx, int64_t 
     hipLaunchKernelGGL(count_errors_kernel, dim3(grid), dim3(64 * kCountWaves), 0, (hipStream_t)stream, dec, dec_ld, tx,
                        tx_ld, rows, n_rows, K, (unsigned long long *)counters);
     return (int)hipGetLastError();
+}
+
+size_t mvn_lstm_workspace_bytes(int64_t B, int32_t T) {
+    if (B < 1 || T < 1) return 0;
+    return kLstmPkFloats * sizeof(float);
+}
+
+int mvn_lstm_decode_f32(const float *y, int64_t y_ld, const float *W_ih0, const float *W_hh0, const float *b_ih0, const float *b_hh0,
+                        const float *W_ih1, const float *W_hh1, const float *b_ih1, const float *b_hh1, const float *fc_W,
+                        const float *fc_b, float *dec, int64_t dec_ld, float *logits, void *workspace, size_t workspace_bytes, int64_t B,
+                        int32_t T, mvn_stream_t stream) {
+    if (B < 0 || T < 1 || y_ld < T || dec_ld < T) return MVN_E_DIMS;
+    if (B == 0) return MVN_OK;
+    const LstmWeights wt = {{W_ih0, W_hh0, b_ih0, b_hh0, W_ih1, W_hh1, b_ih1, b_hh1, fc_W, fc_b}};
+    if (!y || !dec || !workspace) return MVN_E_NULL;
+    for (const float *p : wt.w)
+        if (!p) return MVN_E_NULL;
+    if (workspace_bytes < kLstmPkFloats * sizeof(float) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
+    return launch_lstm_decode(y, y_ld, wt, dec, dec_ld, logits, (float *)workspace, B, T, (hipStream_t)stream);
+}
+
+int mvn_lstm_decode_kernel_name(int64_t B, int32_t T, char *name, int32_t name_len) {
+    if (B < 0 || T < 1) return MVN_E_DIMS;
+    if (!name || name_len < 1) return MVN_E_NULL;
+    snprintf(name, (size_t)name_len, "lstm_pack_kernel + lstm_decode_kernel<1> x %lld", (long long)((B + 15) / 16));
+    return MVN_OK;
 }
 
 }  // extern "C"

@@ -244,6 +244,11 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
 
+    from .lstm import LSTMDetector, MetaLSTMDetector
+
+    if (self_supervised or online_meta) and isinstance(detector, (LSTMDetector, MetaLSTMDetector)):
+        raise ValueError("eval_by_word: online training / meta-learning of the LSTM detector is not built (lstm_trainer.py, "
+                         "meta_lstm_trainer.py); run it without self_supervised and online_meta")
     N = tx.shape[0]
     ser_by_word = np.zeros(N)
     K = tx.shape[1]
