@@ -34,12 +34,6 @@ struct StepShared {
     int s_loc[NS + 4];  // the error locator and its {length, leading zeros}, from the lane that ran Berlekamp-Massey
 };
 
-__device__ __forceinline__ void step_wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Everything of a block step after the detection, by ONE wave (the caller's): sh.dbits holds the detected word (data step),
 // sh.txrow the transmitted message as bytes, sh.gf the tables (and sh.gen the generator polynomial when NS > 2); word r's
 // outputs as in mvn_vnet_byword_step_f32.
@@ -53,7 +47,6 @@ __device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int 
     int *gen = sh.gen, *s_loc = sh.s_loc;
     unsigned char *row = sh.row, *txrow = sh.txrow, *dbits = sh.dbits, *lwb = sh.lwb;
     const int n = T >> 3, k = n - nsym;
-    auto wave_lds_fence = [] { step_wave_fence(); };
     // ---- one wave (the deciding wave; wave 0 on a pilot): the codec on the word's byte image
     int nerr = 0;
     if (!pilot) {
@@ -212,7 +205,7 @@ __global__ __launch_bounds__(64 * kCoopWaves, 4) void byword_step_kernel(
         if (role != kCoopDecided) return;  // the wave that made the decisions carries on with the codec
         if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);  // (after the detector's workgroup barrier: tables complete)
     }
-    step_wave_fence();
+    wave_lds_fence();
     byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, pilot);
 }
 
@@ -244,8 +237,8 @@ __global__ __launch_bounds__(64) void byword_step_va_kernel(
             dbits[t] = (unsigned char)mydec;
         });
     }
-    step_wave_fence();  // (one wave: its own LDS writes -- tables, bytes, decisions -- are visible to all its lanes)
+    wave_lds_fence();  // (one wave: its own LDS writes -- tables, bytes, decisions -- are visible to all its lanes)
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
-    step_wave_fence();
+    wave_lds_fence();
     byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, pilot);
 }

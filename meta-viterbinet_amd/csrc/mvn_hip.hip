@@ -12,7 +12,7 @@
 //                          exact k-ordered fmaf chains == torch-CPU sgemm result order.
 //   count_errors_kernel    metrics.py:7-17 as int64 counters.
 // and, in the .inc files included below (each starts with its own description):
-//   vnet16_fusedn.inc / vnet16_fused.inc   fused ViterbiNet detector at 16 states (MLP on MFMA + in-place DPP sweep)
+//   vnet16_fusedn.inc / vnet16_common.inc  fused ViterbiNet detector at 16 states (MLP on MFMA + in-place DPP sweep)
 //   sweep16_rows / _lds / _quad.inc        16-state sweeps over materialised costs (register prefetch, LDS-DMA)
 //   sweep_inplace.inc                      the same sweep for any other S >= 4 (in-place recurrence + LDS-DMA)
 //   va16_quad.inc, va_inplace.inc          fused classical Viterbi (16 states; any S >= 4)
@@ -70,6 +70,14 @@ __device__ __forceinline__ float expf_u10(float d) {
     u = 1.0f + __builtin_fmaf(s * s, u, s);
     return ldexpf(u, q);
 }
+
+// orders a wave's LDS writes before its own later reads (wave-private images: no other wave touches them)
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ __forceinline__ float sigmoid_from_neg(float d) {
     return 1.0f / (1.0f + expf_u10(d));  // IEEE division (hipcc default: correctly rounded)
 }
@@ -96,7 +104,7 @@ __device__ __forceinline__ float va_cost(float y, float prior) {
 // -------------------------------------------------------------------------------------------
 enum { MODE_COST = 0, MODE_NEGLOGIT = 1, MODE_VA = 2 };
 
-constexpr float kStrictMinBoundG = 1e14f;  // = kStrictMinBound (vnet16_fused.inc, included below)
+constexpr float kStrictMinBoundG = 1e14f;  // = kStrictMinBound (vnet16_common.inc, included below)
 struct GuardWeights {  // the ViterbiNet weights a MODE_NEGLOGIT guard scans (lengths in floats); unused otherwise
     const float *w[6];
     int n[6];
@@ -207,18 +215,14 @@ __global__ __launch_bounds__(64 * kSweepWaves) void sweep_kernel(
                     if (MODE == MODE_NEGLOGIT) c = -c;
                     row[sl + LPB * r] = m[r] + c;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     int p0 = (2 * (sl + LPB * r)) % S;
                     float2 v = *reinterpret_cast<const float2 *>(&row[p0]);
                     m[r] = min2_torch_dev(v.x, v.y);
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
             }
         }
         if (active && sl < TC && t0 + sl < T) dec[b * dec_ld + t0 + sl] = mydec;
@@ -424,7 +428,7 @@ int ensure_dynamic_lds(const void *fn, size_t bytes);  // raises a kernel's dyna
 
 #include "sweep_surv.inc"
 
-#include "vnet16_fused.inc"
+#include "vnet16_common.inc"
 #include "vnet16_fusedn.inc"
 #include "vnet16_dealt.inc"
 #include "vnet16_coop.inc"

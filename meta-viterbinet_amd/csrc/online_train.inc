@@ -71,7 +71,7 @@ __device__ int g_diag_on;
 #define TRAIN_STAMP_WAVE(PH) do {} while (0)
 #endif
 
-// N sigmoids of a thread.  The fast form (vnet16_fused.inc) is exact inside its range |z| <= 86 -- the same value as the full
+// N sigmoids of a thread.  The fast form (vnet16_common.inc) is exact inside its range |z| <= 86 -- the same value as the full
 // form, bit for bit -- so which of the two runs cannot be seen in the result: the wave takes the fast form when ALL its lanes are
 // inside the range (always, in practice) and the full form for all lanes otherwise.  (Round 3 selected per lane, which makes the
 // compiler evaluate BOTH forms for every element: 55 instead of 20 instructions per sigmoid, a third of a chunk's vector work.)

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64 * kLdsWaves) void sweep16_lds_kernel(const float
     };
     // full = all 16 steps of the chunk exist: no per-step branches, so the scheduler can overlap the (independent)
     // decision chains with the recurrence of the following steps
-    bool strict = false;  // wave-uniform, sticky: an odd cost (NaN, infinite, huge: odd_cost(), vnet16_fused.inc) has come by
+    bool strict = false;  // wave-uniform, sticky: an odd cost (NaN, infinite, huge: odd_cost(), vnet16_common.inc) has come by
     auto process_chunk = [&](int c, auto full, auto strict_c) {
         constexpr bool ST = decltype(strict_c)::value;
         const int t0 = 16 * c;

@@ -105,7 +105,7 @@ __device__ __forceinline__ void quad_stage(float (&m)[4], const float (&c)[4]) {
     }
 }
 
-// the same two with torch.min's / torch.argmin's NaN rule (taken from the first odd cost on, odd_cost() in vnet16_fused.inc): the
+// the same two with torch.min's / torch.argmin's NaN rule (taken from the first odd cost on, odd_cost() in vnet16_common.inc): the
 // pairs joined by the previous stage still hold equal metrics (the strict stage writes one value to both partners)
 template <int RHO>
 __device__ __forceinline__ int quad_decide_strict(const float (&m)[4], const int (&U)[4]) {
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(64) void sweep16_quad_kernel(const float *__restric
                 }
                 consume_chunk(k);
                 if (more) issue_chunk(c + kQuadRing, k);
-                // Every cost is tested for oddness (any_odd_cost, vnet16_fused.inc).  A lone wave per SIMD pays every extra
+                // Every cost is tested for oddness (any_odd_cost, vnet16_common.inc).  A lone wave per SIMD pays every extra
                 // instruction's latency, so on whole chunks the test is computed BESIDE the recurrence it does not depend on (one
                 // basic block: the scheduler interleaves the two) and a chunk that turns out to hold an odd cost is processed
                 // again from the saved metrics with the NaN-propagating forms; its decisions are stored over the first ones.

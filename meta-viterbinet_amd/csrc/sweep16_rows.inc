@@ -1,12 +1,12 @@
 // sweep16_rows.inc -- 16-state (L=4) trellis sweep, one 16-lane ROW per block, 4 blocks per wave.
-// Included by mvn_hip.hip inside its anonymous namespace, after vnet16_fused.inc (shares the DPP helpers).
+// Included by mvn_hip.hip inside its anonymous namespace, after vnet16_common.inc (shares the DPP helpers).
 //
 // This is the HBM-bound kernel of the path (mvn_acs_sweep_f32 at S=16: 64 B of branch costs read and
 // 4 B of decision written per symbol) and, with MODE_VA, the fused classical Viterbi detector
 // (costs computed in registers from y and the state priors: 8 B/symbol).
 //
 //   - lane = physical slot of a state vector; the ACS recurrence runs in place exactly as in
-//     vnet16_fused.inc (partner masks 1,2,7,8, logical state of a slot rotates with period 4), so a
+//     vnet16_common.inc (partner masks 1,2,7,8, logical state of a slot rotates with period 4), so a
 //     stage is v_add_f32 + v_min_f32_dpp;
 //   - each lane loads the branch cost of the LOGICAL state it holds at that step straight from HBM
 //     (cost[b][t][logical(p, t%4)]): the 16 lanes of a row still cover one contiguous 64-B line, so
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void sweep16_rows_kernel(
                 for (int i = 0; i < kRowsDepth; ++i) cur[i] = buf[k][i];
                 if (t0 + kRowsDepth * kRowsBufs < T) load_chunk(t0 + kRowsDepth * kRowsBufs, buf[k]);
                 float mydec = 0.0f;
-                if (MODE != MODE_VA && !strict) {  // materialised costs: an odd one (vnet16_fused.inc) switches the wave to torch.min's
+                if (MODE != MODE_VA && !strict) {  // materialised costs: an odd one (vnet16_common.inc) switches the wave to torch.min's
                     strict = __any(any_odd_cost(cur)) != 0;  // rule for good; the classical Viterbi mode is vouched for by its guard launch
                 }
                 auto steps = [&](auto strict_c) {

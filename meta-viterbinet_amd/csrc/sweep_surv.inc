@@ -46,9 +46,7 @@ __global__ __launch_bounds__(64 * kSweepWaves) void sweep_surv_kernel(
 
     // the survivor bytes of stages [t_lo, t_hi) of this wave's blocks, from the staging buffer to surv[b][t_lo ..][.]
     auto flush = [&](int t_lo, int t_hi) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_fence();
         const int nbytes = (t_hi - t_lo) * SB;
 #pragma unroll
         for (int gg = 0; gg < G; ++gg) {
@@ -67,9 +65,7 @@ __global__ __launch_bounds__(64 * kSweepWaves) void sweep_surv_kernel(
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_fence();
     };
 
     float mydec = 0.0f;
@@ -106,9 +102,7 @@ __global__ __launch_bounds__(64 * kSweepWaves) void sweep_surv_kernel(
                     float c = MODE == MODE_VA ? va_cost(yv, pr[r]) : base[(int64_t)t * S + sl + LPB * r];
                     row[sl + LPB * r] = MODE == MODE_NEGLOGIT ? m[r] - c : m[r] + c;  // (ViterbiNet: branch cost = -logit, vnet_detector.py:57)
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
                 const int tb = (t - t_flushed) * SB;  // byte offset of this stage in the staging buffers
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
@@ -126,9 +120,7 @@ __global__ __launch_bounds__(64 * kSweepWaves) void sweep_surv_kernel(
                         else sbuf[wave][g][tb] = (unsigned char)bits;
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
                 if (t + 1 - t_flushed == KS || t + 1 == T) {
                     flush(t_flushed, t + 1);
                     t_flushed = t + 1;

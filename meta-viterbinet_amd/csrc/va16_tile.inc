@@ -24,10 +24,9 @@ __device__ __forceinline__ float va16_tile_block(const float *__restrict__ yb, c
         pr[r] = prior_row[ulog[r]];  // prior of the logical state this lane holds at phase r
     }
     // a non-finite (or absurdly large) state prior makes SOME of a symbol's branch costs NaN: torch.min's NaN rule applies
-    // (vnet16_fused.inc); wave-uniform, decided once
+    // (vnet16_common.inc); wave-uniform, decided once
     const bool strict = __any(needs_strict_min(pr[0]) | needs_strict_min(pr[1]) | needs_strict_min(pr[2]) | needs_strict_min(pr[3]));
-    const int row_time = (q == 2 ? 12 : q == 3 ? 8 : 4 * q);  // rows sweep in the order 0, 1, 3, 2
-    const bool live0 = q == 0, live1 = q == 1, live2 = q == 3, live3 = q == 2;
+    const int row_time = row_time_of(q);  // rows sweep in the order 0, 1, 3, 2
     float m = 0.0f;  // va_detector.py:84
 
     float ynext[4], prec[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // prec: metrics recorded in the previous tile
@@ -47,39 +46,19 @@ __device__ __forceinline__ float va16_tile_block(const float *__restrict__ yb, c
         // The decisions of the PREVIOUS tile (four independent DPP reductions over its recorded metrics) are issued between
         // the phases of this tile's sweep: a lone wave issues in order, so they fill the stall slots of the recurrence's
         // dependent add -> min chain instead of following it.
-        int d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+        int d[4] = {0, 0, 0, 0};
         auto sweep_tile = [&](auto full, auto strict_c) {
             constexpr bool F = decltype(full)::value, ST = decltype(strict_c)::value;
-#define MVN_ACS(R) (ST ? acs_inplace_strict<R>(m, cost[R]) : acs_inplace<R>(m, cost[R]))
-#define MVN_DECIDE(R) (ST ? decide_lsb_strict<R>(prec[R], ulog[R]) : decide_lsb<R>(prec[R], ulog[R]))
-#define MVN_PHASE(PH, LIVE)                                                                            \
-    {                                                                                                  \
-        if (F || 4 * PH + 0 < nsteps) { if (LIVE) mrec[0] = m; m = MVN_ACS(0); }                       \
-        if (F || 4 * PH + 1 < nsteps) { if (LIVE) mrec[1] = m; m = MVN_ACS(1); }                       \
-        if (F || 4 * PH + 2 < nsteps) { if (LIVE) mrec[2] = m; m = MVN_ACS(2); }                       \
-        if (F || 4 * PH + 3 < nsteps) { if (LIVE) mrec[3] = m; m = MVN_ACS(3); }                       \
-    }
-            MVN_PHASE(0, live0)
-            d0 = MVN_DECIDE(0);
-            m = row_handoff<0>(m);  // row 1 <- row 0
-            MVN_PHASE(1, live1)
-            d1 = MVN_DECIDE(1);
-            m = row_handoff<1>(m);  // row 3 <- row 1
-            MVN_PHASE(2, live2)
-            d2 = MVN_DECIDE(2);
-            m = row_handoff<2>(m);  // row 2 <- row 3
-            MVN_PHASE(3, live3)
-            d3 = MVN_DECIDE(3);
-            m = row_handoff<3>(m);  // row 0 <- row 2
-#undef MVN_PHASE
-#undef MVN_DECIDE
-#undef MVN_ACS
+            sweep16_tile<F, ST, false>(m, cost, mrec, nsteps, 0, q, [&](auto ph) {
+                constexpr int R = decltype(ph)::value;
+                d[R] = decide16<R, ST>(prec[R], ulog[R]);
+            });
         };
         if (strict) sweep_tile(std::false_type{}, std::true_type{});
         else if (nsteps == 16) sweep_tile(std::true_type{}, std::false_type{});
         else sweep_tile(std::false_type{}, std::false_type{});
         if (tu > 0) {  // emit the previous tile's 16 decisions (a full tile: only the last one can be partial)
-            const float mydec = (float)(j == 0 ? d0 : j == 1 ? d1 : j == 2 ? d2 : d3);
+            const float mydec = (float)(j == 0 ? d[0] : j == 1 ? d[1] : j == 2 ? d[2] : d[3]);
             if (j < 4) emit(tu - 16 + row_time + j, mydec);
         }
 #pragma unroll
@@ -87,15 +66,7 @@ __device__ __forceinline__ float va16_tile_block(const float *__restrict__ yb, c
     }
     {  // the last tile's decisions
         const int tu = ((T - 1) >> 4) << 4, nsteps = T - tu;
-        int d0, d1, d2, d3;
-        if (!strict) {
-            d0 = decide_lsb<0>(prec[0], ulog[0]), d1 = decide_lsb<1>(prec[1], ulog[1]);
-            d2 = decide_lsb<2>(prec[2], ulog[2]), d3 = decide_lsb<3>(prec[3], ulog[3]);
-        } else {
-            d0 = decide_lsb_strict<0>(prec[0], ulog[0]), d1 = decide_lsb_strict<1>(prec[1], ulog[1]);
-            d2 = decide_lsb_strict<2>(prec[2], ulog[2]), d3 = decide_lsb_strict<3>(prec[3], ulog[3]);
-        }
-        const float mydec = (float)(j == 0 ? d0 : j == 1 ? d1 : j == 2 ? d2 : d3);
+        const float mydec = strict ? decide4<true>(prec, ulog, j) : decide4<false>(prec, ulog, j);
         if (j < 4 && row_time + j < nsteps) emit(tu + row_time + j, mydec);
     }
     return m;
@@ -134,10 +105,9 @@ __global__ __launch_bounds__(64 * kVaSplitWaves) void va16_split_kernel(const fl
         pr[r] = prior_row[ulog[r]];
     }
     const bool strict = __any(needs_strict_min(pr[0]) | needs_strict_min(pr[1]) | needs_strict_min(pr[2]) | needs_strict_min(pr[3]));
-    const int row_time = (q == 2 ? 12 : q == 3 ? 8 : 4 * q);  // rows sweep in the order 0, 1, 3, 2
+    const int row_time = row_time_of(q);  // rows sweep in the order 0, 1, 3, 2
     const int ntiles = (T + 15) >> 4;
     if (wave == 0) {  // ---- the recurrence
-        const bool live0 = q == 0, live1 = q == 1, live2 = q == 3, live3 = q == 2;
         float m = 0.0f;  // va_detector.py:84
         float ynext[4];
 #pragma unroll
@@ -154,30 +124,9 @@ __global__ __launch_bounds__(64 * kVaSplitWaves) void va16_split_kernel(const fl
             // (the live row keeps its metrics before every step with a v_cndmask; exec-masked ds_writes straight into LDS instead were
             // measured slower: 34 vs 28 us for 100 x 1000)
             float mrec[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            auto sweep_tile = [&](auto full, auto strict_c) {
-                constexpr bool F = decltype(full)::value, ST = decltype(strict_c)::value;
-#define MVN_ACS(R) (ST ? acs_inplace_strict<R>(m, cost[R]) : acs_inplace<R>(m, cost[R]))
-#define MVN_PHASE(PH, LIVE)                                                                            \
-    {                                                                                                  \
-        if (F || 4 * PH + 0 < nsteps) { if (LIVE) mrec[0] = m; m = MVN_ACS(0); }                       \
-        if (F || 4 * PH + 1 < nsteps) { if (LIVE) mrec[1] = m; m = MVN_ACS(1); }                       \
-        if (F || 4 * PH + 2 < nsteps) { if (LIVE) mrec[2] = m; m = MVN_ACS(2); }                       \
-        if (F || 4 * PH + 3 < nsteps) { if (LIVE) mrec[3] = m; m = MVN_ACS(3); }                       \
-    }
-                MVN_PHASE(0, live0)
-                m = row_handoff<0>(m);  // row 1 <- row 0
-                MVN_PHASE(1, live1)
-                m = row_handoff<1>(m);  // row 3 <- row 1
-                MVN_PHASE(2, live2)
-                m = row_handoff<2>(m);  // row 2 <- row 3
-                MVN_PHASE(3, live3)
-                m = row_handoff<3>(m);  // row 0 <- row 2
-#undef MVN_PHASE
-#undef MVN_ACS
-            };
-            if (strict) sweep_tile(std::false_type{}, std::true_type{});
-            else if (nsteps == 16) sweep_tile(std::true_type{}, std::false_type{});
-            else sweep_tile(std::false_type{}, std::false_type{});
+            if (strict) sweep16_tile<false, true, false>(m, cost, mrec, nsteps, 0, q);
+            else if (nsteps == 16) sweep16_tile<true, false, false>(m, cost, mrec, nsteps, 0, q);
+            else sweep16_tile<false, false, false>(m, cost, mrec, nsteps, 0, q);
             va_split_rec[(tu >> 4) * 64 + lane] = make_float4(mrec[0], mrec[1], mrec[2], mrec[3]);
             __hip_atomic_store(&s_swept, (tu >> 4) + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -191,15 +140,7 @@ __global__ __launch_bounds__(64 * kVaSplitWaves) void va16_split_kernel(const fl
         while (__hip_atomic_load(&s_swept, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= tile) __builtin_amdgcn_s_sleep(1);
         const float4 p4 = va_split_rec[tile * 64 + lane];
         const float prec[4] = {p4.x, p4.y, p4.z, p4.w};
-        int d0, d1, d2, d3;
-        if (!strict) {
-            d0 = decide_lsb<0>(prec[0], ulog[0]), d1 = decide_lsb<1>(prec[1], ulog[1]);
-            d2 = decide_lsb<2>(prec[2], ulog[2]), d3 = decide_lsb<3>(prec[3], ulog[3]);
-        } else {
-            d0 = decide_lsb_strict<0>(prec[0], ulog[0]), d1 = decide_lsb_strict<1>(prec[1], ulog[1]);
-            d2 = decide_lsb_strict<2>(prec[2], ulog[2]), d3 = decide_lsb_strict<3>(prec[3], ulog[3]);
-        }
-        const float mydec = (float)(j == 0 ? d0 : j == 1 ? d1 : j == 2 ? d2 : d3);
+        const float mydec = strict ? decide4<true>(prec, ulog, j) : decide4<false>(prec, ulog, j);
         if (j < 4 && 16 * tile + row_time + j < T) decb[16 * tile + row_time + j] = mydec;
     }
 }

@@ -109,7 +109,7 @@ __device__ __forceinline__ void va_ip_acs(float (&m)[4], const float (&a)[4], in
 
 // ---- torch.min's NaN rule for the in-place family (the fused ViterbiNet kernel of vnet_fused_ip.inc when a weight is non-finite
 // or huge; the sweeps over materialised costs from the first cost that is NaN, infinite or huge: sweep_inplace.inc)
-__device__ __forceinline__ int va_ip_key(float v) { return strict_key(v); }  // (vnet16_fused.inc)
+__device__ __forceinline__ int va_ip_key(float v) { return strict_key(v); }  // (vnet16_common.inc)
 
 template <int K>
 __device__ __forceinline__ float va_ip_lane_partner(float v, int lane) {

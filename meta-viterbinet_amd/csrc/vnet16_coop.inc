@@ -4,8 +4,8 @@
 // runs at 56 % of a SIMD's rate and a block's T symbols are then a T x 344 ns serial chain (0.34 ms for T = 1000, 42 us for
 // the by-word evaluation's B = 1, T = 136 call).  The only serial part of the detector is the trellis sweep; the likelihood
 // MLP is independent per symbol.  Here a whole 16-wave workgroup serves one block:
-//   phase 1  every wave takes 16-symbol tiles round-robin and runs the MLP exactly like the fused kernel (same k-ordered
-//            fmaf chains: MFMA for hidden units 0..47, the v_fmac chain through LDS for units 48, 49, layer 3 transposed),
+//   phase 1  every wave takes 16-symbol tiles round-robin and runs the fused kernel's MLP (vnet16_common.inc: k-ordered fmaf
+//            chains, MFMA for hidden units 0..47, the v_fmac chain through LDS for units 48, 49, layer 3 transposed), one tile in flight,
 //            and writes the branch costs -logit[t][state] to an LDS buffer (64 B per symbol);
 //   phase 2  after one barrier, wave 0 sweeps the T symbols (in-place DPP recurrence, v_permlane*_swap row hand-off -- the
 //            code of the fused kernel) reading each step's costs from LDS, and wave 1 follows one tile behind with the
@@ -31,16 +31,8 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
                                                  float *m_out, Sink sink) {
     constexpr int S = 16;
     __shared__ int s_swept;  // tiles whose recorded metrics wave 0 has handed over
-    __shared__ float ldsB3w[kK3Steps * 64];
-    __shared__ float2 ldsA2xy[kK2Steps * 64];
-    __shared__ float ldsA2z[kK2Steps * 64];
-    __shared__ float2 ldsWB[kK2Steps * 4];
-    __shared__ float4 ldsB2[3 * 4];
-    __shared__ float4 ldsW4849[kK2Steps * 2];
+    __shared__ Vnet16Image img;              // the weights (vnet16_common.inc)
     __shared__ float4 ldsT[kCoopWaves][80];  // per wave: [symbol][k-phase] image (16 float4) / [symbol j][20] transpose image
-    __shared__ float ldsMax[2];
-    __shared__ float ldsB3[S];
-    __shared__ float ldsB2L[2];
     extern __shared__ float costs[];         // [16 * tiles][16]: -logit of (time, state)
 
     const int lane = threadIdx.x & 63;
@@ -48,157 +40,36 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
     const int j = lane & 15;
     const int q = lane >> 4;
 
-    bool odd_w = false;  // a weight that makes the NaN-propagating ACS minimum necessary (vnet16_fused.inc)
-    for (int e = threadIdx.x; e < kK3Steps * 64; e += blockDim.x) {
-        const int l = e & 63, i3 = e >> 6, k = 4 * i3 + (l >> 4);
-        const float w3 = k < kH2 ? W3[(l & 15) * kH2 + k] : 0.0f;
-        ldsB3w[e] = w3;
-        odd_w |= needs_strict_min(w3);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 64; e += blockDim.x) {
-        const int l = e & 63, i = e >> 6, k = 4 * i + (l >> 4);
-        const float wx = W2[(l & 15) * kH1 + k], wy = W2[(16 + (l & 15)) * kH1 + k], wz = W2[(32 + (l & 15)) * kH1 + k];
-        ldsA2xy[e] = make_float2(wx, wy);
-        ldsA2z[e] = wz;
-        odd_w |= needs_strict_min(wx) | needs_strict_min(wy) | needs_strict_min(wz);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 4; e += blockDim.x) {
-        ldsWB[e] = make_float2(-W1[e], -b1[e]);
-        odd_w |= needs_strict_min(W1[e]) | needs_strict_min(b1[e]);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 2; e += blockDim.x) {
-        const float *wr = W2 + (48 + (e & 1)) * kH1 + 4 * (e >> 1);
-        ldsW4849[e] = make_float4(wr[0], wr[1], wr[2], wr[3]);
-        odd_w |= needs_strict_min(wr[0]) | needs_strict_min(wr[1]) | needs_strict_min(wr[2]) | needs_strict_min(wr[3]);
-    }
-    if (threadIdx.x < kH2) odd_w |= needs_strict_min(b2[threadIdx.x]);
-    if (threadIdx.x < 12) {
-        const int u0 = 16 * (threadIdx.x >> 2) + 4 * (threadIdx.x & 3);
-        ldsB2[threadIdx.x] = make_float4(b2[u0], b2[u0 + 1], b2[u0 + 2], b2[u0 + 3]);
-    }
-    if (wave == 0) {
-        float wm = fmaxf(fabsf(W1[lane]), lane + 64 < kH1 ? fabsf(W1[lane + 64]) : 0.0f);
-        float bm = fmaxf(fabsf(b1[lane]), lane + 64 < kH1 ? fabsf(b1[lane + 64]) : 0.0f);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            wm = fmaxf(wm, __shfl_xor(wm, off));
-            bm = fmaxf(bm, __shfl_xor(bm, off));
-        }
-        if (lane == 0) {
-            ldsMax[0] = wm;
-            ldsMax[1] = bm;
-        }
-    }
-    if (threadIdx.x < S) {
-        ldsB3[threadIdx.x] = b3[threadIdx.x];
-        odd_w |= needs_strict_min(b3[threadIdx.x]);
-    }
-    if (threadIdx.x < 2) ldsB2L[threadIdx.x] = b2[48 + threadIdx.x];
+    const bool odd_w = img.stage(W1, b1, W2, b2, W3, b3);
     const bool strict = __syncthreads_or(odd_w) != 0;  // the prologue's barrier; workgroup-uniform
-    const float wmax = ldsMax[0], bmax = ldsMax[1];
+    const float wmax = img.ldsMax[0], bmax = img.ldsMax[1];
 
     const int tiles = (T + 15) >> 4;
     float4 *const tbase = &ldsT[wave][0];
-    auto wave_lds_fence = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    const int sym_time = ((j >> 2) == 2 ? 12 : (j >> 2) == 3 ? 8 : 4 * (j >> 2)) + (j & 3);
-    const int row_time = (q == 2 ? 12 : q == 3 ? 8 : 4 * q);
+    const int sym_time = sym_time_of(j), row_time = row_time_of(q);
     const int cunit = (lane >> 4) & 1;  // this lane's unit chain: symbol (lane & 15), unit 48 + cunit (lanes >= 32 duplicate)
     float *const tbw = reinterpret_cast<float *>(tbase) + 4 * j + q;
     float4 *const tbr = tbase + j;
-    float4 *const ttw = tbase + 5 * j + q;
-    const float *const ttr = reinterpret_cast<const float *>(tbase + 5 * j) + q;
 
     // ---------------------------------------------------------------- phase 1: the MLP, one 16-symbol tile per wave and trip
     for (int tile = wave; tile < tiles; tile += kCoopWaves) {
         const int tu = 16 * tile;
         const int ty = tu + sym_time;
-        const float yv = yb[ty < T ? ty : T - 1];
-        const bool fast = __all(fabsf(yv) * wmax + bmax <= kFastSigmoidBound);
-        f32x4 acc[3];
+        const float yv[1] = {yb[ty < T ? ty : T - 1]};
+        const bool fast = __all(fabsf(yv[0]) * wmax + bmax <= kFastSigmoidBound);
+        f32x4 acc[1][3];
 #pragma unroll
-        for (int tau = 0; tau < 3; ++tau) acc[tau] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float ca = 0.0f;
-        auto chain_step = [&](const float4 tr, const float4 wa) {
-            ca = __builtin_fmaf(wa.x, tr.x, ca);
-            ca = __builtin_fmaf(wa.y, tr.y, ca);
-            ca = __builtin_fmaf(wa.z, tr.z, ca);
-            ca = __builtin_fmaf(wa.w, tr.w, ca);
-        };
-        auto layer2 = [&](auto sigmoid) {
-            for (int i0 = 0; i0 < kK2Steps; i0 += 5) {
-#pragma unroll
-                for (int ii = 0; ii < 5; ++ii) {
-                    const int i = i0 + ii;
-                    const float2 axy = ldsA2xy[i * 64 + lane];
-                    const float az = ldsA2z[i * 64 + lane];
-                    const float2 wb = ldsWB[i * 4 + q];
-                    float4 tr = make_float4(0.f, 0.f, 0.f, 0.f), wa = tr;
-                    if (i > 0) {
-                        tr = *tbr;
-                        wa = ldsW4849[2 * (i - 1) + cunit];
-                    }
-                    wave_lds_fence();
-                    const float h = sigmoid(__builtin_fmaf(yv, wb.x, wb.y));
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.x, h, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.y, h, acc[1], 0, 0, 0);
-                    acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(az, h, acc[2], 0, 0, 0);
-                    *tbw = h;
-                    if (i > 0) chain_step(tr, wa);
-                    wave_lds_fence();
-                }
-            }
-            chain_step(*tbr, ldsW4849[2 * (kK2Steps - 1) + cunit]);
-        };
-        if (fast)
-            layer2([](float d) { return sigmoid_from_neg_fast(d); });
-        else
-            layer2([](float d) { return sigmoid_from_neg(d); });
-
-        // units 48, 49 -> bias + ReLU -> back through the image (k-phases 2, 3 of the last operand are zero)
-        wave_lds_fence();
-        {
-            const float za = ca + ldsB2L[cunit];
-            float *slot = reinterpret_cast<float *>(tbr) + cunit;
-            slot[0] = za < 0.0f ? 0.0f : za;
-            slot[2] = 0.0f;
-        }
-        wave_lds_fence();
-        const float hl = *tbw;
-        wave_lds_fence();
-
-        float bop[13];
-#pragma unroll
-        for (int tau = 0; tau < 3; ++tau) {
-            const float4 bb = ldsB2[tau * 4 + q];
-            const float bbr[4] = {bb.x, bb.y, bb.z, bb.w};
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float z = acc[tau][r] + bbr[r];
-                v[r] = z < 0.0f ? 0.0f : z;  // relu; NaN propagates like torch's
-            }
-            *ttw = make_float4(v[0], v[1], v[2], v[3]);
-            wave_lds_fence();
-#pragma unroll
-            for (int r = 0; r < 4; ++r) bop[4 * tau + r] = ttr[4 * r];
-            wave_lds_fence();
-        }
-        bop[12] = hl;
-        f32x4 acc3 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i3 = 0; i3 < kK3Steps; ++i3)
-            acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(bop[i3], ldsB3w[i3 * 64 + lane], acc3, 0, 0, 0);
-        const float b3s = ldsB3[j];
+        for (int tau = 0; tau < 3; ++tau) acc[0][tau] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float ch[1] = {0.0f}, hl[1], logit[1][4];
+        if (fast) vnet16_kloop<1, false>([](float d) { return sigmoid_from_neg_fast(d); }, img, yv, lane, cunit, tbw, tbr, acc, ch);
+        else vnet16_kloop<1, false>([](float d) { return sigmoid_from_neg(d); }, img, yv, lane, cunit, tbw, tbr, acc, ch);
+        vnet16_units4849(img, cunit, tbw, tbr, ch, hl);
+        vnet16_tile_pass<1>(img, tbase, lane, acc, hl, logit);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {  // lane (state j, row q): time 4 q' + r of the tile
-            const float logit = acc3[r] + b3s;
             const int tl = tu + row_time + r;
-            if (WRITE_LOGITS && tl < T) logits_b[(int64_t)tl * S + j] = logit;
-            costs[tl * S + j] = -logit;  // vnet_detector.py:57
+            if (WRITE_LOGITS && tl < T) logits_b[(int64_t)tl * S + j] = logit[0][r];
+            costs[tl * S + j] = -logit[0][r];  // vnet_detector.py:57
         }
     }
     if (threadIdx.x == 0) s_swept = 0;
@@ -213,7 +84,6 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
 #pragma unroll
     for (int r = 0; r < 4; ++r) ulog[r] = logical_state(j, r);
     if (wave == 0) {
-        const bool live0 = q == 0, live1 = q == 1, live2 = q == 3, live3 = q == 2;
         float m = 0.0f;
         for (int tile = 0; tile < tiles; ++tile) {
             const int tu = 16 * tile;
@@ -223,30 +93,9 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
             for (int r = 0; r < 4; ++r) cost[r] = costs[(tu + row_time + r) * S + ulog[r]];  // the lane's logical state at phase r
             float mrec[4];
             mrec[0] = mrec[1] = mrec[2] = mrec[3] = 0.0f;
-            auto sweep_tile = [&](auto full, auto strict_c) {
-                constexpr bool F = decltype(full)::value, ST = decltype(strict_c)::value;
-#define MVN_ACS(R) (ST ? acs_inplace_strict<R>(m, cost[R]) : acs_inplace<R>(m, cost[R]))
-#define MVN_PHASE(PH, LIVE)                                                                            \
-    {                                                                                                  \
-        if (F || 4 * PH + 0 < nsteps) { if (LIVE) mrec[0] = m; m = MVN_ACS(0); }                       \
-        if (F || 4 * PH + 1 < nsteps) { if (LIVE) mrec[1] = m; m = MVN_ACS(1); }                       \
-        if (F || 4 * PH + 2 < nsteps) { if (LIVE) mrec[2] = m; m = MVN_ACS(2); }                       \
-        if (F || 4 * PH + 3 < nsteps) { if (LIVE) mrec[3] = m; m = MVN_ACS(3); }                       \
-    }
-                MVN_PHASE(0, live0)
-                m = row_handoff<0>(m);  // row 1 <- row 0
-                MVN_PHASE(1, live1)
-                m = row_handoff<1>(m);  // row 3 <- row 1
-                MVN_PHASE(2, live2)
-                m = row_handoff<2>(m);  // row 2 <- row 3
-                MVN_PHASE(3, live3)
-                m = row_handoff<3>(m);  // row 0 <- row 2
-#undef MVN_PHASE
-#undef MVN_ACS
-            };
-            if (strict) sweep_tile(std::false_type{}, std::true_type{});  // torch.min's NaN rule (vnet16_fused.inc)
-            else if (nsteps == 16) sweep_tile(std::true_type{}, std::false_type{});
-            else sweep_tile(std::false_type{}, std::false_type{});
+            if (strict) sweep16_tile<false, true, false>(m, cost, mrec, nsteps, 0, q);  // torch.min's NaN rule (vnet16_common.inc)
+            else if (nsteps == 16) sweep16_tile<true, false, false>(m, cost, mrec, nsteps, 0, q);
+            else sweep16_tile<false, false, false>(m, cost, mrec, nsteps, 0, q);
             reinterpret_cast<float4 *>(costs + tu * S)[lane] = make_float4(mrec[0], mrec[1], mrec[2], mrec[3]);
             __hip_atomic_store(&s_swept, tile + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -258,16 +107,9 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
         const int nsteps = T - tu < 16 ? T - tu : 16;
         const int tdec = tu + row_time + j;
         while (__hip_atomic_load(&s_swept, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= tile) __builtin_amdgcn_s_sleep(1);
-        const float4 mrec = reinterpret_cast<const float4 *>(costs + tu * S)[lane];
-        int d0, d1, d2, d3;
-        if (!strict) {
-            d0 = decide_lsb<0>(mrec.x, ulog[0]), d1 = decide_lsb<1>(mrec.y, ulog[1]);
-            d2 = decide_lsb<2>(mrec.z, ulog[2]), d3 = decide_lsb<3>(mrec.w, ulog[3]);
-        } else {
-            d0 = decide_lsb_strict<0>(mrec.x, ulog[0]), d1 = decide_lsb_strict<1>(mrec.y, ulog[1]);
-            d2 = decide_lsb_strict<2>(mrec.z, ulog[2]), d3 = decide_lsb_strict<3>(mrec.w, ulog[3]);
-        }
-        const float mydec = (float)(j == 0 ? d0 : j == 1 ? d1 : j == 2 ? d2 : d3);
+        const float4 mr4 = reinterpret_cast<const float4 *>(costs + tu * S)[lane];
+        const float mrec[4] = {mr4.x, mr4.y, mr4.z, mr4.w};
+        const float mydec = strict ? decide4<true>(mrec, ulog, j) : decide4<false>(mrec, ulog, j);
         if (j < 4) sink(tdec, mydec, row_time + j < nsteps);
     }
     return kCoopDecided;

@@ -1,5 +1,5 @@
 // vnet16_dealt.inc -- the fused 16-state ViterbiNet detector with its work dealt in 32-symbol UNITS instead of whole blocks
-// (included by mvn_hip.hip after vnet16_fusedn.inc, whose k-loop, tile phase and helpers it repeats).
+// (included by mvn_hip.hip after vnet16_fusedn.inc; the unit's arithmetic -- k-loop, tile pass, sweep, decisions -- is vnet16_common.inc's).
 //
 // vnet16_fusedn_kernel gives every block to one wave.  A block of 1000 symbols is 0.8 ms of a wave's life at 6 waves per SIMD, so
 // the launch is quantised in blocks: BASELINE's 10 000 blocks are 9.77 per SIMD -- ten on most, in a 6-wave round and a 4-wave
@@ -56,17 +56,9 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
     constexpr int NT = 2;
     constexpr int S = 16;
     constexpr int kSym = 16 * NT;
-    __shared__ float ldsB3w[kK3Steps * 64];
-    __shared__ float2 ldsA2xy[kK2Steps * 64];
-    __shared__ float ldsA2z[kK2Steps * 64];
-    __shared__ float2 ldsWB[kK2Steps * 4];
-    __shared__ float4 ldsB2[3 * 4];
-    __shared__ float4 ldsW4849[kK2Steps * 2];
+    __shared__ Vnet16Image img;                 // the weights (vnet16_common.inc)
     __shared__ float4 ldsT[kDealtWaves][160];   // per wave: the [symbol][k-phase] image of the k-loop / two [symbol j][20] transposition images
-    __shared__ float ldsMax[2];
-    __shared__ float ldsB3[S];
-    __shared__ float ldsB2L[2];
-    __shared__ int4 ldsLane[64];
+    __shared__ Vnet16LaneStates lanes;
     __shared__ float ldsHand[kDealtWaves][20];  // slot w: the path metrics (row-0 lane order) wave w last published, [16] = abandoned
     __shared__ int ldsSeq[kDealtWaves];         // ... for the unit with this execution number + 1
     __shared__ int ldsCarry[kDealtWaves];       // counting launches: the block's bit errors up to and including that unit ...
@@ -77,55 +69,8 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 15;
 
-    bool odd_w = false;
-    for (int e = threadIdx.x; e < kK3Steps * 64; e += blockDim.x) {
-        const int l = e & 63, i3 = e >> 6, k = 4 * i3 + (l >> 4);
-        const float w3 = k < kH2 ? W3[(l & 15) * kH2 + k] : 0.0f;
-        ldsB3w[e] = w3;
-        odd_w |= needs_strict_min(w3);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 64; e += blockDim.x) {
-        const int l = e & 63, i = e >> 6, k = 4 * i + (l >> 4);
-        const float wx = W2[(l & 15) * kH1 + k], wy = W2[(16 + (l & 15)) * kH1 + k], wz = W2[(32 + (l & 15)) * kH1 + k];
-        ldsA2xy[e] = make_float2(wx, wy);
-        ldsA2z[e] = wz;
-        odd_w |= needs_strict_min(wx) | needs_strict_min(wy) | needs_strict_min(wz);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 4; e += blockDim.x) {
-        ldsWB[e] = make_float2(-W1[e], -b1[e]);
-        odd_w |= needs_strict_min(W1[e]) | needs_strict_min(b1[e]);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 2; e += blockDim.x) {
-        const float *wr = W2 + (48 + (e & 1)) * kH1 + 4 * (e >> 1);
-        ldsW4849[e] = make_float4(wr[0], wr[1], wr[2], wr[3]);
-        odd_w |= needs_strict_min(wr[0]) | needs_strict_min(wr[1]) | needs_strict_min(wr[2]) | needs_strict_min(wr[3]);
-    }
-    if (threadIdx.x < kH2) odd_w |= needs_strict_min(b2[threadIdx.x]);
-    if (threadIdx.x < 12) {
-        const int u0 = 16 * (threadIdx.x >> 2) + 4 * (threadIdx.x & 3);
-        ldsB2[threadIdx.x] = make_float4(b2[u0], b2[u0 + 1], b2[u0 + 2], b2[u0 + 3]);
-    }
-    if (wave == 0) {
-        float wm = fmaxf(fabsf(W1[lane]), lane + 64 < kH1 ? fabsf(W1[lane + 64]) : 0.0f);
-        float bm = fmaxf(fabsf(b1[lane]), lane + 64 < kH1 ? fabsf(b1[lane + 64]) : 0.0f);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            wm = fmaxf(wm, __shfl_xor(wm, off));
-            bm = fmaxf(bm, __shfl_xor(bm, off));
-        }
-        if (lane == 0) {
-            ldsMax[0] = wm;
-            ldsMax[1] = bm;
-        }
-    }
-    if (threadIdx.x < S) {
-        ldsB3[threadIdx.x] = b3[threadIdx.x];
-        odd_w |= needs_strict_min(b3[threadIdx.x]);
-    }
-    if (threadIdx.x < 2) ldsB2L[threadIdx.x] = b2[48 + threadIdx.x];
-    if (threadIdx.x < 64)
-        ldsLane[threadIdx.x] = make_int4(logical_state(threadIdx.x & 15, 0), logical_state(threadIdx.x & 15, 1),
-                                         logical_state(threadIdx.x & 15, 2), logical_state(threadIdx.x & 15, 3));
+    const bool odd_w = img.stage(W1, b1, W2, b2, W3, b3);
+    lanes.stage();
     if (threadIdx.x < kDealtWaves) {
         ldsSeq[threadIdx.x] = 0;
         ldsSeqC[threadIdx.x] = 0;
@@ -133,8 +78,8 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<int *>(ws) = 0;  // the status word (an abandoned wait sets it, seconds later)
     const bool strict = __syncthreads_or(odd_w) != 0;  // the prologue's barrier; workgroup-uniform.  No barrier below.
-    const float wmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ldsMax[0])));
-    const float bmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ldsMax[1])));
+    const float wmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(img.ldsMax[0])));
+    const float bmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(img.ldsMax[1])));
 
     // ---- this ring's range of the launch's units and the order it executes them in (all wave-uniform: scalar registers).
     // A ring is `ring` = 8, 4, 2 or 1 consecutive waves of the workgroup: ring 4 = one wave per SIMD, all of the same age on it.
@@ -152,15 +97,7 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
     auto unit_pos = [&](int e) { return e < n_head ? hi - n_head + e : e < n_head + n_mid ? lo + n_tail + (e - n_head) : lo + (e - n_head - n_mid); };
 
     float4 *const tbase = &ldsT[wave][0];
-    auto sym_time_of = [](int jj) { return ((jj >> 2) == 2 ? 12 : (jj >> 2) == 3 ? 8 : 4 * (jj >> 2)) + (jj & 3); };
-    auto row_time_of = [](int qq) { return qq == 2 ? 12 : qq == 3 ? 8 : 4 * qq; };
     const int q = lane >> 4;
-    const bool live0 = q == 0, live1 = q == 1, live2 = q == 3, live3 = q == 2;
-    auto wave_lds_fence = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
 
 #ifdef MVN_DIAG_PHASES  // diagnostic build only (tools/diag_phases.py): cycles per phase, summed over the wave's units
     unsigned long long dg[6] = {0, 0, 0, 0, 0, 0};
@@ -253,7 +190,7 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
         const int qk = lane_k >> 4;
         float *const tbw = reinterpret_cast<float *>(tbase) + 4 * (lane_k & 15) + qk;
         float4 *const tbr = tbase + (lane_k & 31);
-        const float4 *const wch = &ldsW4849[lane_k >> 5];
+        const int cunit = lane_k >> 5;  // this lane's unit chain: symbol (lane & 31), unit 48 + cunit
         float yv[NT];
         {
             const float *yb2 = y + (int64_t)b2 * y_ld;  // the next unit's samples are requested now
@@ -273,70 +210,17 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
         for (int u = 0; u < NT; ++u)
 #pragma unroll
             for (int tau = 0; tau < 3; ++tau) acc[u][tau] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float ca = 0.0f;
-        auto chain_step = [&](const float4 tr, const float4 wa) {
-            ca = __builtin_fmaf(wa.x, tr.x, ca);
-            ca = __builtin_fmaf(wa.y, tr.y, ca);
-            ca = __builtin_fmaf(wa.z, tr.z, ca);
-            ca = __builtin_fmaf(wa.w, tr.w, ca);
-        };
-        // ntl = the unit's live tiles: a block's last unit may end within its first tile (T = 1000: 8 symbols), and then runs the
+        float ch[1] = {0.0f};
+        // the unit's live tiles: a block's last unit may end within its first tile (T = 1000: 8 symbols), and then runs the
         // k-loop for that tile alone -- half the MFMAs and sigmoids (tile 1's accumulators stay 0; nothing of tile 1 is used)
-        auto layer2 = [&](auto sigmoid, auto ntl) {
-            constexpr int NTL = decltype(ntl)::value;
-            for (int i0 = 0; i0 < kK2Steps; i0 += 5) {
-#pragma unroll
-                for (int ii = 0; ii < 5; ++ii) {
-                    const int i = i0 + ii;
-                    const float2 axy = ldsA2xy[i * 64 + lane_k];
-                    const float az = ldsA2z[i * 64 + lane_k];
-                    const float2 wb = ldsWB[i * 4 + qk];
-                    float4 tr = make_float4(0.f, 0.f, 0.f, 0.f), wa = tr;
-                    if (i > 0) {
-                        tr = *tbr;
-                        wa = wch[2 * (i - 1)];
-                    }
-                    wave_lds_fence();
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < NTL; ++u) {
-                        const float h = sigmoid(__builtin_fmaf(yv[u], wb.x, wb.y));
-                        acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.x, h, acc[u][0], 0, 0, 0);
-                        acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.y, h, acc[u][1], 0, 0, 0);
-                        acc[u][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(az, h, acc[u][2], 0, 0, 0);
-                        tbw[64 * u] = h;
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if (i > 0) chain_step(tr, wa);
-                    wave_lds_fence();
-                }
-            }
-            wave_lds_fence();
-            chain_step(*tbr, wch[2 * (kK2Steps - 1)]);
-        };
         const bool one_tile = t0 + 16 >= T;
-        if (fast && !one_tile)
-            layer2([](float d) { return sigmoid_from_neg_fast(d); }, std::integral_constant<int, 2>{});
-        else if (!one_tile)
-            layer2([](float d) { return sigmoid_from_neg(d); }, std::integral_constant<int, 2>{});
-        else if (fast)
-            layer2([](float d) { return sigmoid_from_neg_fast(d); }, std::integral_constant<int, 1>{});
-        else
-            layer2([](float d) { return sigmoid_from_neg(d); }, std::integral_constant<int, 1>{});
+        if (fast && !one_tile) vnet16_kloop<2, true>([](float d) { return sigmoid_from_neg_fast(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
+        else if (!one_tile) vnet16_kloop<2, true>([](float d) { return sigmoid_from_neg(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
+        else if (fast) vnet16_kloop<1, true>([](float d) { return sigmoid_from_neg_fast(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
+        else vnet16_kloop<1, true>([](float d) { return sigmoid_from_neg(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
 
         float hl[NT];
-        {
-            wave_lds_fence();
-            const float za = ca + ldsB2L[lane_k >> 5];
-            const float ra = za < 0.0f ? 0.0f : za;
-            float *slot = reinterpret_cast<float *>(tbr) + (lane_k >> 5);
-            slot[0] = ra;
-            slot[2] = 0.0f;
-            wave_lds_fence();
-#pragma unroll
-            for (int u = 0; u < NT; ++u) hl[u] = tbw[64 * u];
-            wave_lds_fence();
-        }
+        vnet16_units4849(img, cunit, tbw, tbr, ch, hl);
 
 #if MVN_FN_PRIO
         __builtin_amdgcn_s_setprio(3);
@@ -354,17 +238,14 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
         asm volatile("" : "+v"(lane_t));
         const int jt = lane_t & 15, qt = lane_t >> 4;
         const int lane4 = 4 * lane_t;
-        const int4 ul4 = ldsLane[lane_t];
+        const int4 ul4 = lanes.ldsLane[lane_t];
         const int ulog[4] = {ul4.x, ul4.y, ul4.z, ul4.w};
         const int row_time = row_time_of(qt);
         float cost[NT][4], mrec[NT][4], txv[NT];
         // ---- pass A, both tiles together (two transposition images per wave, the two layer-3 chains interleaved: the phase is
         // latency, not work).  Tile 1 is evaluated even when the block ended in tile 0 (n1 == 0): nothing of it is stored or swept.
         {
-            float4 *const ttw = tbase + 5 * jt + qt;                                        // + 80 u
-            const float *const ttr = reinterpret_cast<const float *>(tbase + 5 * jt) + qt;  // + 320 u
             const int row_addr = 4 * (lane_t & 48);
-            float bop[NT][13];
 #pragma unroll
             for (int u = 0; u < NT; ++u) {
                 const int tdec = t0 + 16 * u + row_time + jt;
@@ -373,50 +254,17 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mrec[u][r] = 0.0f;
             }
-#pragma unroll
-            for (int tau = 0; tau < 3; ++tau) {
-                const float4 bb = ldsB2[tau * 4 + qt];
-                const float bbr[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-                for (int u = 0; u < NT; ++u) {
-                    float v[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float z = acc[u][tau][r] + bbr[r];
-                        v[r] = z < 0.0f ? 0.0f : z;
-                    }
-                    ttw[80 * u] = make_float4(v[0], v[1], v[2], v[3]);
-                }
-                wave_lds_fence();
-#pragma unroll
-                for (int u = 0; u < NT; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) bop[u][4 * tau + r] = ttr[320 * u + 4 * r];
-                wave_lds_fence();
-            }
-            f32x4 acc3[NT];
-#pragma unroll
-            for (int u = 0; u < NT; ++u) {
-                bop[u][12] = hl[u];
-                acc3[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int i3 = 0; i3 < kK3Steps; ++i3) {
-                const float w3 = ldsB3w[i3 * 64 + lane_t];
-#pragma unroll
-                for (int u = 0; u < NT; ++u) acc3[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(bop[u][i3], w3, acc3[u], 0, 0, 0);
-            }
-            const float b3s = ldsB3[jt];
+            float logit[NT][4];
+            vnet16_tile_pass<NT>(img, tbase, lane_t, acc, hl, logit);
 #pragma unroll
             for (int u = 0; u < NT; ++u)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float logit = acc3[u][r] + b3s;
                     if (WRITE_LOGITS) {
                         const int tl = t0 + 16 * u + row_time + r;
-                        if (tl < T) logits_out[((int64_t)b * T + tl) * S + jt] = logit;
+                        if (tl < T) logits_out[((int64_t)b * T + tl) * S + jt] = logit[u][r];
                     }
-                    cost[u][r] = -__int_as_float(__builtin_amdgcn_ds_bpermute(row_addr + 4 * ulog[r], __float_as_int(logit)));
+                    cost[u][r] = -__int_as_float(__builtin_amdgcn_ds_bpermute(row_addr + 4 * ulog[r], __float_as_int(logit[u][r])));
                 }
         }
 
@@ -455,36 +303,15 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
         }
         MVN_DG_LAP(2)
         // ... the two sweeps ...
-        auto sweep_tile = [&](auto full, auto strict_c, float (&c4)[4], float (&rec)[4], const int nsteps) {
-            constexpr bool F = decltype(full)::value, ST = decltype(strict_c)::value;
-#define MVN_ACS(R) (ST ? acs_inplace_strict<R>(m, c4[R]) : acs_inplace<R>(m, c4[R]))
-#define MVN_PHASE(PH, LIVE)                                                                          \
-    {                                                                                                \
-        if (F || 4 * PH + 0 < nsteps) { if (LIVE) rec[0] = m; m = MVN_ACS(0); }                       \
-        if (F || 4 * PH + 1 < nsteps) { if (LIVE) rec[1] = m; m = MVN_ACS(1); }                       \
-        if (F || 4 * PH + 2 < nsteps) { if (LIVE) rec[2] = m; m = MVN_ACS(2); }                       \
-        if (F || 4 * PH + 3 < nsteps) { if (LIVE) rec[3] = m; m = MVN_ACS(3); }                       \
-    }
-            MVN_PHASE(0, live0)
-            m = bperm_off<192>(lane4, m);
-            MVN_PHASE(1, live1)
-            m = bperm_off<128>(lane4, m);
-            MVN_PHASE(2, live2)
-            m = bperm_off<64>(lane4, m);
-            MVN_PHASE(3, live3)
-            m = bperm_off<128>(lane4, m);
-#undef MVN_PHASE
-#undef MVN_ACS
-        };
         if (!strict && n1 == 16) {  // (the common case: both tiles whole)
-            sweep_tile(std::true_type{}, std::false_type{}, cost[0], mrec[0], 16);
-            sweep_tile(std::true_type{}, std::false_type{}, cost[1], mrec[1], 16);
+            sweep16_tile<true, false, true>(m, cost[0], mrec[0], 16, lane4, q);
+            sweep16_tile<true, false, true>(m, cost[1], mrec[1], 16, lane4, q);
         } else if (!strict) {
-            sweep_tile(std::false_type{}, std::false_type{}, cost[0], mrec[0], n0);
-            if (n1 > 0) sweep_tile(std::false_type{}, std::false_type{}, cost[1], mrec[1], n1);
+            sweep16_tile<false, false, true>(m, cost[0], mrec[0], n0, lane4, q);
+            if (n1 > 0) sweep16_tile<false, false, true>(m, cost[1], mrec[1], n1, lane4, q);
         } else {
-            sweep_tile(std::false_type{}, std::true_type{}, cost[0], mrec[0], n0);
-            if (n1 > 0) sweep_tile(std::false_type{}, std::true_type{}, cost[1], mrec[1], n1);
+            sweep16_tile<false, true, true>(m, cost[0], mrec[0], n0, lane4, q);
+            if (n1 > 0) sweep16_tile<false, true, true>(m, cost[1], mrec[1], n1, lane4, q);
         }
         // ... and on to the wave that sweeps the block's next unit
         if (s + 1 < U) {
@@ -520,15 +347,7 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
             {  // (both tiles unconditionally: one basic block, the two tiles' DPP chains interleave; n1 == 0 stores nothing)
                 const int nsteps = u == 0 ? n0 : n1;
                 const int tdec = t0 + 16 * u + row_time + jt;
-                int d0, d1, d2, d3;
-                if (!strict) {
-                    d0 = decide_lsb<0>(mrec[u][0], ulog[0]), d1 = decide_lsb<1>(mrec[u][1], ulog[1]);
-                    d2 = decide_lsb<2>(mrec[u][2], ulog[2]), d3 = decide_lsb<3>(mrec[u][3], ulog[3]);
-                } else {
-                    d0 = decide_lsb_strict<0>(mrec[u][0], ulog[0]), d1 = decide_lsb_strict<1>(mrec[u][1], ulog[1]);
-                    d2 = decide_lsb_strict<2>(mrec[u][2], ulog[2]), d3 = decide_lsb_strict<3>(mrec[u][3], ulog[3]);
-                }
-                float mydec = (float)(jt == 0 ? d0 : jt == 1 ? d1 : jt == 2 ? d2 : d3);
+                float mydec = strict ? decide4<true>(mrec[u], ulog, jt) : decide4<false>(mrec[u], ulog, jt);
                 if (bad) mydec = __int_as_float(0x7fc00000);  // an abandoned hand-off: no decision is claimed
                 if (jt < 4 && row_time + jt < nsteps) {
                     if (decb) decb[tdec] = mydec;

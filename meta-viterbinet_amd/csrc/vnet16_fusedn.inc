@@ -1,5 +1,5 @@
 // vnet16_fusedn.inc -- fused ViterbiNet detector for 16 states, NT 16-symbol tiles per super-tile (included by
-// mvn_hip.hip after vnet16_fused.inc, whose sigmoid / DPP / sweep helpers it shares).
+// mvn_hip.hip after vnet16_common.inc, which holds the unit's arithmetic: weight image, k-loop, tile pass, sweep, decisions).
 //
 // One wavefront owns one block (word) for all T symbols; a workgroup is 8 independent waves sharing one LDS image of the
 // weights.  Arithmetic and operation order are those of the reference (exact k-ordered fmaf chains, SLEEF sigmoid), so logits
@@ -18,7 +18,7 @@
 //     unit 48 and lanes 32..63 unit 49 of symbol (lane & 31).
 //   * the results go back to the layer-3 operand layout (row q = k-phase) through the same LDS image, and so do the
 //     (q,r) transposes of the D-layout tiles.
-// Layer 3, the in-place DPP sweep and the decisions are per 16-symbol tile, as in vnet16_fused.inc.
+// Layer 3, the in-place DPP sweep and the decisions are per 16-symbol tile, as in vnet16_common.inc.
 #ifndef MVN_FN_WAVES
 #define MVN_FN_WAVES 8  // waves (= blocks) per workgroup, sharing one LDS image of the weights
 #endif
@@ -30,31 +30,10 @@
 #endif
 constexpr int kFusedNWaves = MVN_FN_WAVES;
 
-// value of lane ((lane + OFF/4) mod 64): ds_bpermute_b32 with the rotation in the instruction's offset field
-template <int OFF>
-__device__ __forceinline__ float bperm_off(int lane4, float v) {
-    float r;
-    asm("ds_bpermute_b32 %0, %1, %2 offset:%3\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lane4), "v"(v), "n"(OFF));
-    return r;
-}
-
-// The same hand-off on the vector ALU (v_permlane{16,32}_swap, ~13 cycles of latency instead of an LDS round trip of ~120):
-// for the kernels whose sweep is a lone wave's critical path (va16_tile.inc, vnet16_coop.inc); the throughput-bound fused
-// kernel uses the LDS crossbar form above, which costs the FP32 pipe nothing.  Only the receiving row's copy is used.
-template <int K>
-__device__ __forceinline__ float row_handoff(float m) {
-    const unsigned mu = __float_as_uint(m);
-    if (K == 0) return __uint_as_float(__builtin_amdgcn_permlane16_swap(mu, mu, false, false)[0]);  // row 1 <- row 0
-    if (K == 1) return __uint_as_float(__builtin_amdgcn_permlane32_swap(mu, mu, false, false)[0]);  // row 3 <- row 1
-    if (K == 2) return __uint_as_float(__builtin_amdgcn_permlane16_swap(mu, mu, false, false)[1]);  // row 2 <- row 3
-    return __uint_as_float(__builtin_amdgcn_permlane32_swap(mu, mu, false, false)[1]);              // row 0 <- row 2
-}
-
 template <int NT>
 struct FusedNCfg {
     // second launch bound = waves per SIMD the kernel is built for (hipcc's meaning of the argument): 5 need <= 96 VGPRs
     static constexpr int kMinWgPerCu = NT <= 2 ? (MVN_FN_WAVES * MVN_FN_WGS + 3) / 4 : 4;
-    static constexpr int kUnroll = 5;                    // k-steps per loop trip (25 k-steps)
 };
 
 template <bool WRITE_LOGITS, int NT>
@@ -67,18 +46,10 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
     static_assert(NT == 2 || NT == 4, "NT = 2 (one unit chain per lane) or 4 (two)");
     constexpr int S = 16;
     constexpr int kSym = 16 * NT;                     // symbols per super-tile
-    __shared__ float ldsB3w[kK3Steps * 64];           // W3 as the layer-3 B operand
-    __shared__ float2 ldsA2xy[kK2Steps * 64];         // (i, lane) -> W2[{0,16} + (lane&15)][4i + (lane>>4)]
-    __shared__ float ldsA2z[kK2Steps * 64];           // (i, lane) -> W2[32 + (lane&15)][4i + (lane>>4)]
-    __shared__ float2 ldsWB[kK2Steps * 4];            // (i, q) -> {-w1, -b1}[4i + q]
-    __shared__ float4 ldsB2[3 * 4];                   // (tau, q) -> b2[16 tau + 4 q + {0,1,2,3}]  (D-layout rows of a lane)
-    __shared__ float4 ldsW4849[kK2Steps * 2];         // (i, row) -> W2[48 + row][4i + {0,1,2,3}]
+    __shared__ Vnet16Image img;                       // the weights (vnet16_common.inc)
     constexpr int kTImg = kSym > 80 ? kSym : 80;      // float4s per wave: [symbol][k-phase] image / [symbol j][20] transpose image
     __shared__ float4 ldsT[kFusedNWaves][kTImg];      // wave-private scratch image (two uses, see below)
-    __shared__ float ldsMax[2];                       // max |W1|, max |b1|
-    __shared__ float ldsB3[S];                        // b3
-    __shared__ float ldsB2L[2];                       // b2[48], b2[49]
-    __shared__ int4 ldsLane[64];                      // per lane: logical state of lane (l & 15) at phases 0..3 (kept out of the VGPRs)
+    __shared__ Vnet16LaneStates lanes;                // per lane: logical state of lane (l & 15) at phases 0..3 (kept out of the VGPRs)
 
 #ifdef MVN_DIAG_STAMPS  // diagnostic build only (tools/ablate_fused.py): wave timeline written over the final-metric rows
     const unsigned long long st_re = __builtin_amdgcn_s_memrealtime();
@@ -88,61 +59,11 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
     const int j = lane & 15;
     const int q = lane >> 4;
 
-    // every weight passes through here once: the staging loops also look for the values that make the NaN-propagating
-    // ACS minimum necessary (vnet16_fused.inc, "torch.min's NaN rule")
-    bool odd_w = false;
-    for (int e = threadIdx.x; e < kK3Steps * 64; e += blockDim.x) {
-        const int l = e & 63, i3 = e >> 6, k = 4 * i3 + (l >> 4);
-        const float w3 = k < kH2 ? W3[(l & 15) * kH2 + k] : 0.0f;
-        ldsB3w[e] = w3;
-        odd_w |= needs_strict_min(w3);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 64; e += blockDim.x) {
-        const int l = e & 63, i = e >> 6, k = 4 * i + (l >> 4);
-        const float wx = W2[(l & 15) * kH1 + k], wy = W2[(16 + (l & 15)) * kH1 + k], wz = W2[(32 + (l & 15)) * kH1 + k];
-        ldsA2xy[e] = make_float2(wx, wy);
-        ldsA2z[e] = wz;
-        odd_w |= needs_strict_min(wx) | needs_strict_min(wy) | needs_strict_min(wz);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 4; e += blockDim.x) {
-        ldsWB[e] = make_float2(-W1[e], -b1[e]);
-        odd_w |= needs_strict_min(W1[e]) | needs_strict_min(b1[e]);
-    }
-    for (int e = threadIdx.x; e < kK2Steps * 2; e += blockDim.x) {
-        const float *wr = W2 + (48 + (e & 1)) * kH1 + 4 * (e >> 1);
-        ldsW4849[e] = make_float4(wr[0], wr[1], wr[2], wr[3]);
-        odd_w |= needs_strict_min(wr[0]) | needs_strict_min(wr[1]) | needs_strict_min(wr[2]) | needs_strict_min(wr[3]);
-    }
-    if (threadIdx.x < kH2) odd_w |= needs_strict_min(b2[threadIdx.x]);
-    if (threadIdx.x < 12) {
-        const int u0 = 16 * (threadIdx.x >> 2) + 4 * (threadIdx.x & 3);
-        ldsB2[threadIdx.x] = make_float4(b2[u0], b2[u0 + 1], b2[u0 + 2], b2[u0 + 3]);
-    }
-    if (wave == 0) {  // max |W1|, max |b1| over the 100 hidden-1 units: two values per lane, xor-butterfly
-        float wm = fmaxf(fabsf(W1[lane]), lane + 64 < kH1 ? fabsf(W1[lane + 64]) : 0.0f);
-        float bm = fmaxf(fabsf(b1[lane]), lane + 64 < kH1 ? fabsf(b1[lane + 64]) : 0.0f);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            wm = fmaxf(wm, __shfl_xor(wm, off));
-            bm = fmaxf(bm, __shfl_xor(bm, off));
-        }
-        if (lane == 0) {
-            ldsMax[0] = wm;
-            ldsMax[1] = bm;
-        }
-    }
-    if (threadIdx.x < S) {
-        ldsB3[threadIdx.x] = b3[threadIdx.x];
-        odd_w |= needs_strict_min(b3[threadIdx.x]);
-    }
-    if (threadIdx.x < 2) ldsB2L[threadIdx.x] = b2[48 + threadIdx.x];
-    if (threadIdx.x < 64)
-        ldsLane[threadIdx.x] = make_int4(logical_state(threadIdx.x & 15, 0), logical_state(threadIdx.x & 15, 1),
-                                         logical_state(threadIdx.x & 15, 2), logical_state(threadIdx.x & 15, 3));
-    // this lane's unit chain(s): NT = 4 -> lane = symbol, units 48 and 49; NT = 2 -> symbol lane & 31, unit 48 + (lane >> 5)
+    const bool odd_w = img.stage(W1, b1, W2, b2, W3, b3);
+    lanes.stage();
     const bool strict = __syncthreads_or(odd_w) != 0;  // the prologue's barrier; workgroup-uniform
-    const float wmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ldsMax[0])));
-    const float bmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ldsMax[1])));
+    const float wmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(img.ldsMax[0])));
+    const float bmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(img.ldsMax[1])));
 
     const int64_t b = (int64_t)blockIdx.x * kFusedNWaves + wave;
     if (b >= B) return;  // whole wave; no barriers below
@@ -152,23 +73,12 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
 
     float4 *const tbase = &ldsT[wave][0];
 
-    // time offset of symbol index i = 4 qi + ri within a tile: rows sweep in the order 0, 1, 3, 2 (recomputed where used)
-    auto sym_time_of = [](int jj) { return ((jj >> 2) == 2 ? 12 : (jj >> 2) == 3 ? 8 : 4 * (jj >> 2)) + (jj & 3); };
-    auto row_time_of = [](int qq) { return qq == 2 ? 12 : qq == 3 ? 8 : 4 * qq; };
-    const bool live0 = q == 0, live1 = q == 1, live2 = q == 3, live3 = q == 2;
-
     const float *yb = y + b * y_ld;
     float *decb = dec ? dec + b * dec_ld : nullptr;
     const bool counted = tx != nullptr && (row_mask == nullptr || row_mask[b] != 0);
     const float *txb = counted ? tx + b * tx_ld : nullptr;
     int nerr = 0;
     float m = 0.0f;
-
-    auto wave_lds_fence = [] {  // orders this wave's LDS writes before its own later reads (no other wave touches ldsT[wave])
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
 
     float ynext[NT];
 #pragma unroll
@@ -204,7 +114,7 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
         const int qk = lane_k >> 4;
         float *const tbw = reinterpret_cast<float *>(tbase) + 4 * (lane_k & 15) + qk;    // + 64 u: (symbol 16u + j, k-phase q)
         float4 *const tbr = tbase + (NT == 4 ? lane_k : (lane_k & 31));                   // this lane's chain symbol
-        const float4 *const wch = &ldsW4849[NT == 4 ? 0 : (lane_k >> 5)];                 // + 2 i (NT = 4: second chain at + 1)
+        const int cunit = NT == 4 ? 0 : (lane_k >> 5);                                    // NT = 2: this lane's unit 48 + cunit
         float yv[NT];
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
@@ -222,79 +132,18 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
         for (int u = 0; u < NT; ++u)
 #pragma unroll
             for (int tau = 0; tau < 3; ++tau) acc[u][tau] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float ca = 0.0f, cb = 0.0f;  // unit chain(s) of this lane (cb: unit 49, NT = 4 only)
-
-        // one k-step (four k's, in order) of this lane's unit chain(s): tr = the four sigmoids of its symbol
-        auto chain_step = [&](const float4 tr, const float4 wa, const float4 wb4) {
-            ca = __builtin_fmaf(wa.x, tr.x, ca);
-            ca = __builtin_fmaf(wa.y, tr.y, ca);
-            ca = __builtin_fmaf(wa.z, tr.z, ca);
-            ca = __builtin_fmaf(wa.w, tr.w, ca);
-            if constexpr (NT == 4) {
-                cb = __builtin_fmaf(wb4.x, tr.x, cb);
-                cb = __builtin_fmaf(wb4.y, tr.y, cb);
-                cb = __builtin_fmaf(wb4.z, tr.z, cb);
-                cb = __builtin_fmaf(wb4.w, tr.w, cb);
-            }
-        };
-        auto layer2 = [&](auto sigmoid) {
-            for (int i0 = 0; i0 < kK2Steps; i0 += FusedNCfg<NT>::kUnroll) {
-#pragma unroll
-                for (int ii = 0; ii < FusedNCfg<NT>::kUnroll; ++ii) {
-                    const int i = i0 + ii;
-                    const float2 axy = ldsA2xy[i * 64 + lane_k];
-                    const float az = ldsA2z[i * 64 + lane_k];
-                    const float2 wb = ldsWB[i * 4 + qk];
-                    // the image still holds k-step i-1: request it now, consume it after this k-step's sigmoids (their
-                    // ds_writes are issued after this read, and a wave's LDS operations execute in order)
-                    float4 tr = make_float4(0.f, 0.f, 0.f, 0.f), wa = tr, wb4 = tr;
-                    if (i > 0) {
-                        tr = *tbr;
-                        wa = wch[2 * (i - 1)];
-                        if constexpr (NT == 4) wb4 = wch[2 * (i - 1) + 1];
-                    }
-                    wave_lds_fence();
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < NT; ++u) {
-                        const float h = sigmoid(__builtin_fmaf(yv[u], wb.x, wb.y));
-                        acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.x, h, acc[u][0], 0, 0, 0);
-                        acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.y, h, acc[u][1], 0, 0, 0);
-                        acc[u][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(az, h, acc[u][2], 0, 0, 0);
-                        tbw[64 * u] = h;
-                        __builtin_amdgcn_sched_barrier(0);  // keep the sigmoids from interleaving (registers)
-                    }
-                    if (i > 0) chain_step(tr, wa, wb4);
-                    wave_lds_fence();
-                }
-            }
-            wave_lds_fence();
-            chain_step(*tbr, wch[2 * (kK2Steps - 1)], NT == 4 ? wch[2 * (kK2Steps - 1) + 1] : make_float4(0.f, 0.f, 0.f, 0.f));
-        };
-        if (fast)
-            layer2([](float d) { return sigmoid_from_neg_fast(d); });
-        else
-            layer2([](float d) { return sigmoid_from_neg(d); });
+        float ch[NT == 4 ? 2 : 1] = {};  // unit chain(s): NT = 4 -> lane = symbol, units 48 and 49; NT = 2 -> symbol lane & 31, unit 48 + (lane >> 5)
+        // (called through a lambda of this kernel, like the sigmoid: see vnet16_kloop)
+        auto kloop = [&](auto sig) { vnet16_kloop<NT, true>(sig, img, yv, lane_k, cunit, tbw, tbr, acc, ch); };
+        if (fast) kloop([](float d) { return sigmoid_from_neg_fast(d); });
+        else kloop([](float d) { return sigmoid_from_neg(d); });
 
         // units 48,49 -> bias + ReLU -> back through the image: tile u's operand wants h2[48 + q] of symbol (16u + j) at row q
         float hl[NT];
-        {
-            wave_lds_fence();
-            const float za = ca + ldsB2L[NT == 4 ? 0 : (lane_k >> 5)];
-            const float ra = za < 0.0f ? 0.0f : za;
-            if constexpr (NT == 4) {
-                const float zb = cb + ldsB2L[1];
-                *tbr = make_float4(ra, zb < 0.0f ? 0.0f : zb, 0.0f, 0.0f);
-            } else {
-                float *slot = reinterpret_cast<float *>(tbr) + (lane_k >> 5);
-                slot[0] = ra;
-                slot[2] = 0.0f;
-            }
-            wave_lds_fence();
-#pragma unroll
-            for (int u = 0; u < NT; ++u) hl[u] = tbw[64 * u];
-            wave_lds_fence();
-        }
+        int lane_e = lane;  // (the epilogue's addresses from a fresh opaque copy of the lane id: the k-loop keeps only what it reads itself)
+        asm volatile("" : "+v"(lane_e));
+        vnet16_units4849(img, NT == 4 ? 0 : (lane_e >> 5), reinterpret_cast<float *>(tbase) + 4 * (lane_e & 15) + (lane_e >> 4),
+                         tbase + (NT == 4 ? lane_e : (lane_e & 31)), ch, hl);
 
 #ifdef MVN_DIAG_PHASES
         {
@@ -317,97 +166,36 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
                 int lane_t = lane;
                 asm volatile("" : "+v"(lane_t));
                 const int jt = lane_t & 15, qt = lane_t >> 4;
-                float4 *const ttw = tbase + 5 * jt + qt;                                        // transpose image: row j, units 4q..4q+3
-                const float *const ttr = reinterpret_cast<const float *>(tbase + 5 * jt) + qt;  // + 4 r': unit 4r' + q of row j
                 const int row_addr = 4 * (lane_t & 48);
                 const int lane4 = 4 * lane_t;  // ds_bpermute addresses wrap at 64 lanes
-                const int4 ul4 = ldsLane[lane_t];
+                const int4 ul4 = lanes.ldsLane[lane_t];
                 const int ulog[4] = {ul4.x, ul4.y, ul4.z, ul4.w};
                 const int row_time = row_time_of(qt);
                 const int tdec = tu + row_time + jt;  // the symbol this lane decides (lanes j < 4 of each row)
                 float txv = 0.0f;  // its transmitted bit, requested now so the latency hides under layer 3
                 if (counted && jt < 4 && tdec < K) txv = txb[tdec];
-                float bop[13];
-                // bias + ReLU in the MFMA's D layout (lane (j,q), register r = unit 16 tau + 4q + r of symbol j), then the
-                // (q,r) transpose that puts k in natural order for layer 3 -- through the wave's LDS image, rows of 20
-                // dwords per symbol (one ds_write_b128 and four conflict-free ds_read_b32 per row tile) instead of four
-                // v_permlane*_swap: LDS instructions cost the SIMD's FP32 pipe nothing, a swap costs it 13 cycles here
-#pragma unroll
-                for (int tau = 0; tau < 3; ++tau) {
-                    const float4 bb = ldsB2[tau * 4 + qt];
-                    const float bbr[4] = {bb.x, bb.y, bb.z, bb.w};
-                    float v[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float z = acc[u][tau][r] + bbr[r];
-                        v[r] = z < 0.0f ? 0.0f : z;  // relu; NaN propagates like torch's
-                    }
-                    *ttw = make_float4(v[0], v[1], v[2], v[3]);
-                    wave_lds_fence();
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) bop[4 * tau + r] = ttr[4 * r];
-                    wave_lds_fence();
-                }
-                bop[12] = hl[u];
-
-                f32x4 acc3 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i3 = 0; i3 < kK3Steps; ++i3)
-                    acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(bop[i3], ldsB3w[i3 * 64 + lane_t], acc3, 0, 0, 0);
-
-                float cost[4];
-                const float b3s = ldsB3[jt];
+                float logit[1][4], cost[4];
+                vnet16_tile_pass<1>(img, tbase, lane_t, acc + u, hl + u, logit);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float logit = acc3[r] + b3s;
                     if (WRITE_LOGITS) {
                         const int tl = tu + row_time + r;
-                        if (tl < T) logits_out[((int64_t)b * T + tl) * S + jt] = logit;
+                        if (tl < T) logits_out[((int64_t)b * T + tl) * S + jt] = logit[0][r];
                     }
-                    cost[r] = -__int_as_float(__builtin_amdgcn_ds_bpermute(row_addr + 4 * ulog[r], __float_as_int(logit)));
+                    cost[r] = -__int_as_float(__builtin_amdgcn_ds_bpermute(row_addr + 4 * ulog[r], __float_as_int(logit[0][r])));
                 }
 
                 float mrec[4];
                 mrec[0] = mrec[1] = mrec[2] = mrec[3] = 0.0f;
-                auto sweep_tile = [&](auto full, auto strict_c) {
-                    constexpr bool F = decltype(full)::value, ST = decltype(strict_c)::value;
-#define MVN_ACS(R) (ST ? acs_inplace_strict<R>(m, cost[R]) : acs_inplace<R>(m, cost[R]))
-#define MVN_PHASE(PH, LIVE)                                                                            \
-    {                                                                                                  \
-        if (F || 4 * PH + 0 < nsteps) { if (LIVE) mrec[0] = m; m = MVN_ACS(0); }                       \
-        if (F || 4 * PH + 1 < nsteps) { if (LIVE) mrec[1] = m; m = MVN_ACS(1); }                       \
-        if (F || 4 * PH + 2 < nsteps) { if (LIVE) mrec[2] = m; m = MVN_ACS(2); }                       \
-        if (F || 4 * PH + 3 < nsteps) { if (LIVE) mrec[3] = m; m = MVN_ACS(3); }                       \
-    }
-                    // a row hands its state vector to the next one through the LDS crossbar (ds_bpermute: no memory, and
-                    // no FP32-pipe time, unlike the v_permlane*_swap it replaces); only the receiving row's copy is used
-                    MVN_PHASE(0, live0)
-                    m = bperm_off<192>(lane4, m);  // row 1 <- row 0 (lane - 16)
-                    MVN_PHASE(1, live1)
-                    m = bperm_off<128>(lane4, m);  // row 3 <- row 1 (lane - 32)
-                    MVN_PHASE(2, live2)
-                    m = bperm_off<64>(lane4, m);   // row 2 <- row 3 (lane + 16)
-                    MVN_PHASE(3, live3)
-                    m = bperm_off<128>(lane4, m);  // row 0 <- row 2 (lane + 32)
-#undef MVN_PHASE
-#undef MVN_ACS
-                };
-                int d0, d1, d2, d3;
-                if (!strict) {
-                    if (nsteps == 16) sweep_tile(std::true_type{}, std::false_type{});
-                    else sweep_tile(std::false_type{}, std::false_type{});
-                    d0 = decide_lsb<0>(mrec[0], ulog[0]), d1 = decide_lsb<1>(mrec[1], ulog[1]);
-                    d2 = decide_lsb<2>(mrec[2], ulog[2]), d3 = decide_lsb<3>(mrec[3], ulog[3]);
-                } else {  // a non-finite or huge weight: torch.min's NaN rule (vnet16_fused.inc)
-                    sweep_tile(std::false_type{}, std::true_type{});
-                    d0 = decide_lsb_strict<0>(mrec[0], ulog[0]), d1 = decide_lsb_strict<1>(mrec[1], ulog[1]);
-                    d2 = decide_lsb_strict<2>(mrec[2], ulog[2]), d3 = decide_lsb_strict<3>(mrec[3], ulog[3]);
-                }
-                const float mydec = (float)(jt == 0 ? d0 : jt == 1 ? d1 : jt == 2 ? d2 : d3);
-                if (jt < 4 && row_time + jt < nsteps) {
-                    if (decb) decb[tdec] = mydec;
-                    if (counted && tdec < K) nerr += ((long long)mydec != (long long)txv) ? 1 : 0;
-                }
+                // (strict: a non-finite or huge weight, torch.min's NaN rule of vnet16_common.inc)
+                if (strict) sweep16_tile<false, true, true>(m, cost, mrec, nsteps, lane4, q);
+                else if (nsteps == 16) sweep16_tile<true, false, true>(m, cost, mrec, nsteps, lane4, q);
+                else sweep16_tile<false, false, true>(m, cost, mrec, nsteps, lane4, q);
+                const float mydec = strict ? decide4<true>(mrec, ulog, jt) : decide4<false>(mrec, ulog, jt);
+                const bool mine = jt < 4 && row_time + jt < nsteps;
+                if (mine && decb) decb[tdec] = mydec;
+                // (counted in a scalar register: a per-lane count would hold a VGPR across the k-loop)
+                if (counted) nerr += __popcll(__ballot(mine && tdec < K && (long long)mydec != (long long)txv));
             }
         }
 #ifdef MVN_DIAG_PHASES
@@ -426,8 +214,6 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
     return;
 #endif
     if (counted) {  // two global atomics per block in error; the bits/frames totals come from count_totals_kernel
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nerr += __shfl_xor(nerr, off);
         if ((threadIdx.x & 63) == 0 && nerr) {  // (thread index re-read here: nothing lane-derived stays live across the main loop)
             atomicAdd(&counters[0], (unsigned long long)nerr);
             atomicAdd(&counters[2], 1ull);
@@ -446,6 +232,8 @@ __global__ __launch_bounds__(64 * kFusedNWaves, FusedNCfg<NT>::kMinWgPerCu) void
         o[4] = ((unsigned long long)xcc << 32) | hw;
     }
 #else
-    if (final_metric && (threadIdx.x & 48) == 0) final_metric[b * S + logical_state(threadIdx.x & 15, T & 3)] = m;  // row 0 holds the metrics
+    int lane_f = lane;  // (opaque: nothing the prologue derived from the lane id is kept across the main loop for this)
+    asm volatile("" : "+v"(lane_f));
+    if (final_metric && lane_f < 16) final_metric[b * S + logical_state(lane_f, T & 3)] = m;  // row 0 holds the metrics
 #endif
 }

@@ -208,11 +208,6 @@ __global__ __launch_bounds__(64 * vnet_ip_waves<LB>(), (vnet_ip_waves<LB>() * vn
     const int nvalid = B - b0 < BPW ? (int)(B - b0) : BPW;
     float *img = &image[wave][0];
     unsigned *dbits = &dbits_all[wave][0];
-    auto wave_lds_fence = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
 
     // image address of (block g, step 0, state 0): see sweep_inplace_kernel.  The lanes of the layout's unused blocks (g >= BPW)
     // shadow block 0: they read valid memory, never write, and no partner operation crosses a block
@@ -239,7 +234,7 @@ __global__ __launch_bounds__(64 * vnet_ip_waves<LB>(), (vnet_ip_waves<LB>() * vn
                 const int blk = g_ < nvalid ? g_ : nvalid - 1;     // past the batch: the last block again, never stored
                 yj[ti] = y[(b0 + blk) * y_ld + step];
                 fsym[ti] = g_ * IMG + j_ * S + 4 * q;  // (block g_, step j_, state 4 q) of the chunk image, before padding
-                // the fast sigmoid is exact inside its range (vnet16_fused.inc): wave-uniform choice, same bits either way
+                // the fast sigmoid is exact inside its range (vnet16_common.inc): wave-uniform choice, same bits either way
                 fast = fast && __all(fabsf(yj[ti]) * wmax + bmax <= kFastSigmoidBound);
             }
             f32x4 acc[TI][4];

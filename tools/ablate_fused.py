@@ -5,6 +5,7 @@ run time is read).  f32 MFMA and every other instruction of a SIMD are mutually 
 taken out.
 
     python tools/ablate_fused.py build        # here (CPU): patched copies of csrc/ -> .scratch/abl/libmvn_<name>.so
+    python tools/ablate_fused.py patch        # the patch step alone: every patched statement still occurs exactly once
     python tools/ablate_fused.py run          # on the GPU box: time every variant (own process each, MVN_LIB_PATH)
 """
 import os
@@ -17,29 +18,31 @@ CSRC = os.path.join(ROOT, "meta-viterbinet_amd", "csrc")
 OUT = os.path.join(ROOT, ".scratch", "abl")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
-SRC = "vnet16_fusedn.inc"
-SWEEP_CALL = """                if (nsteps == 16) sweep_tile(std::true_type{});
-                else sweep_tile(std::false_type{});"""
-DECIDE = """                const int d0 = decide_lsb<0>(mrec[0], ulog[0]), d1 = decide_lsb<1>(mrec[1], ulog[1]);
-                const int d2 = decide_lsb<2>(mrec[2], ulog[2]), d3 = decide_lsb<3>(mrec[3], ulog[3]);"""
-L3 = "                    acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(bop[i3], ldsB3w[i3 * 64 + lane], acc3, 0, 0, 0);"
-SIG = "                        const float h = sigmoid(__builtin_fmaf(yv[u], wb.x, wb.y));"
-MF2 = """                        acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.x, h, acc[u][0], 0, 0, 0);
-                        acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.y, h, acc[u][1], 0, 0, 0);
-                        acc[u][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(az, h, acc[u][2], 0, 0, 0);"""
-CHAIN = "                    if (i > 0) chain_step(tr, wa, wb4);"
+# The patched statements: the kernel's own file holds its block loop and the calls, vnet16_common.inc the unit's arithmetic
+# (shared with the dealt and the cooperative kernel: their results are wrong too in a patched build; only this kernel is timed).
+KERNEL, COMMON = "vnet16_fusedn.inc", "vnet16_common.inc"
+SWEEP_CALL = """                if (strict) sweep16_tile<false, true, true>(m, cost, mrec, nsteps, lane4, q);
+                else if (nsteps == 16) sweep16_tile<true, false, true>(m, cost, mrec, nsteps, lane4, q);
+                else sweep16_tile<false, false, true>(m, cost, mrec, nsteps, lane4, q);"""
+DECIDE = "                const float mydec = strict ? decide4<true>(mrec, ulog, jt) : decide4<false>(mrec, ulog, jt);"
+L3 = "        for (int u = 0; u < NTT; ++u) acc3[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(bop[u][i3], w3, acc3[u], 0, 0, 0);"
+SIG = "                const float h = sigmoid(__builtin_fmaf(yv[u], wb.x, wb.y));"
+MF2 = """                acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.x, h, acc[u][0], 0, 0, 0);
+                acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(axy.y, h, acc[u][1], 0, 0, 0);
+                acc[u][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(az, h, acc[u][2], 0, 0, 0);"""
+CHAIN = "            if (i > 0) chain_step(tr, wa, wb4);"
 TILE = "            if (tu < T) {  // wave-uniform"
 
-# phase knock-outs: patched copies of the kernel source (results wrong by construction, only the time is read)
+# phase knock-outs: (file, statement, replacement) applied to a copy of csrc/ (results wrong by construction, only the time is read)
 VARIANTS = {
     "base": [],
-    "nosweep": [(SWEEP_CALL, "                m += cost[0] + cost[1] + cost[2] + cost[3]; mrec[0] = m; mrec[1] = cost[1]; mrec[2] = cost[2]; mrec[3] = cost[3];")],
-    "nodecide": [(DECIDE, "                const int d0 = __float_as_int(mrec[0]) & 1, d1 = __float_as_int(mrec[1]) & 1, d2 = __float_as_int(mrec[2]) & 1, d3 = __float_as_int(mrec[3]) & 1;")],
-    "nol3": [(L3, "                    acc3[i3 & 3] += bop[i3] * ldsB3w[i3 * 64 + lane];")],
-    "nosig": [(SIG, "                        const float h = __builtin_fmaf(yv[u], wb.x, wb.y);")],
-    "nomfma2": [(MF2, "                        acc[u][0][0] += axy.x * h; acc[u][1][1] += axy.y * h; acc[u][2][2] += az * h;")],
-    "nochain": [(CHAIN, "                    if (i > 0) ca += tr.x * wa.x;")],
-    "notile": [(TILE, "            if (tu < T && yv[0] == 12345.0f) {  // wave-uniform")],
+    "nosweep": [(KERNEL, SWEEP_CALL, "                m += cost[0] + cost[1] + cost[2] + cost[3]; mrec[0] = m; mrec[1] = cost[1]; mrec[2] = cost[2]; mrec[3] = cost[3];")],
+    "nodecide": [(KERNEL, DECIDE, "                const float mydec = (float)(__float_as_int(mrec[jt & 3]) & 1);")],
+    "nol3": [(COMMON, L3, "        for (int u = 0; u < NTT; ++u) acc3[u][i3 & 3] += bop[u][i3] * w3;")],
+    "nosig": [(COMMON, SIG, "                const float h = __builtin_fmaf(yv[u], wb.x, wb.y);")],
+    "nomfma2": [(COMMON, MF2, "                acc[u][0][0] += axy.x * h; acc[u][1][1] += axy.y * h; acc[u][2][2] += az * h;")],
+    "nochain": [(COMMON, CHAIN, "            if (i > 0) ch[0] += tr.x * wa.x;")],
+    "notile": [(KERNEL, TILE, "            if (tu < T && yv[0] == 12345.0f) {  // wave-uniform")],
 }
 
 # variants that only differ by -D switches of the product source
@@ -54,26 +57,35 @@ for _k in DEFS:
     VARIANTS.setdefault(_k, [])
 
 
-def build():
+def patched_tree(name):
+    """A copy of csrc/ and include/ under OUT with the variant's statements replaced; every statement must occur exactly once."""
+    d = os.path.join(OUT, "src_" + name)
+    shutil.rmtree(d, ignore_errors=True)
+    csrc = os.path.join(d, "meta-viterbinet_amd", "csrc")
+    shutil.copytree(CSRC, csrc)
+    shutil.copytree(os.path.join(ROOT, "include"), os.path.join(d, "include"))
+    for fname, old, new in VARIANTS[name]:
+        p = os.path.join(csrc, fname)
+        s = open(p).read()
+        assert s.count(old) == 1, (name, fname, old[:60], s.count(old))
+        open(p, "w").write(s.replace(old, new))
+    return d
+
+
+def build(compile_=True):
     os.makedirs(OUT, exist_ok=True)
-    for name, patches in VARIANTS.items():
+    for name in VARIANTS:
         if sys.argv[2:] and name not in sys.argv[2:]:
             continue
-        d = os.path.join(OUT, "src_" + name)
-        shutil.rmtree(d, ignore_errors=True)
-        shutil.copytree(CSRC, os.path.join(d, "meta-viterbinet_amd", "csrc"))
-        shutil.copytree(os.path.join(ROOT, "include"), os.path.join(d, "include"))
-        p = os.path.join(d, "meta-viterbinet_amd", "csrc", SRC)
-        s = open(p).read()
-        for old, new in patches:
-            assert s.count(old) == 1, (name, old[:60], s.count(old))
-            s = s.replace(old, new)
-        open(p, "w").write(s)
-        so = os.path.join(OUT, f"libmvn_{name}.so")
-        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + DEFS.get(name, []) + [os.path.join(d, "meta-viterbinet_amd", "csrc", "mvn_hip.hip"), "-o", so],
-                       check=True)
+        d = patched_tree(name)
+        if compile_:
+            so = os.path.join(OUT, f"libmvn_{name}.so")
+            subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + DEFS.get(name, []) + [os.path.join(d, "meta-viterbinet_amd", "csrc", "mvn_hip.hip"), "-o", so],
+                           check=True)
+            print("built", so, flush=True)
+        else:
+            print("patched", name, flush=True)
         shutil.rmtree(d)
-        print("built", so, flush=True)
 
 
 TIMER = r"""
@@ -139,4 +151,4 @@ def run():
 
 
 if __name__ == "__main__":
-    {"build": build, "run": run}[sys.argv[1]]()
+    {"build": build, "patch": lambda: build(compile_=False), "run": run}[sys.argv[1]]()
