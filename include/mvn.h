@@ -453,6 +453,41 @@ int mvn_lstm_decode_f32(const float *y, int64_t y_ld, const float *W_ih0, const 
                         int32_t T, mvn_stream_t stream);
 int mvn_lstm_decode_kernel_name(int64_t B, int32_t T, char *name, int32_t name_len);
 
+/* Training of the same network in one launch (lstm_train.inc): n_iter x {forward 'train' on ONE word, CrossEntropyLoss(mean) of the
+ * two logits against the word's bits, backward through time, optimizer step}, the loop of LSTMTrainer.online_training
+ * (trainers/LSTM/lstm_trainer.py:42-53), MetaLSTMTrainer.online_training (trainers/META_LSTM/meta_lstm_trainer.py:48-60) and the
+ * inner loop of Trainer.train() (trainer.py:470-479).
+ *   y [n_words, T] (row stride y_ld), bits int32 [n_words, T] in {0,1} (row stride bits_ld): iteration i trains on word
+ *   word_of_iter[i] (NULL: word 0 in every iteration = online training).
+ *   M > 0: the loss of iteration i is the mean over the M positions idx[i * M .. i * M + M) (select_batch, trainer.py:534-544; a
+ *   position drawn twice counts twice); M == 0: over all T positions (idx is not read).
+ *   The ten tensors (order and layout of mvn_lstm_decode_f32) and exp_avg / exp_avg_sq ([795138] floats, parameters() order) are
+ *   updated in place; step0 = optimizer steps taken before the call.  beta1 >= 0: Adam (torch defaults, amsgrad off);
+ *   beta1 = MVN_BETA1_RMSPROP: RMSprop with alpha = beta2 (exp_avg_sq is the square average, exp_avg is left alone);
+ *   beta1 = MVN_BETA1_SGD: SGD (neither is touched).  loss_out [n_iter] or NULL.
+ *   workspace: mvn_lstm_train_workspace_bytes(T) bytes of device memory, 16-byte aligned, private to the call while it runs.
+ *   status: device int32 or NULL, set to 1 if a device-wide wait was abandoned (the weights are then NaN; MVN_E_BARRIER's text).
+ * 1 <= T <= 256 (MVN_LSTM_TRAIN_MAX_T: the saved activations of all T steps share the LDS with the weight slices); the launch
+ * uses 64 workgroups and returns MVN_E_DEVICE on a device with fewer CUs.  MVN_E_DIMS for T out of range, a row stride < T,
+ * n_iter < 0, M < 0, M > T, n_words < 1 or step0 < 0 (checked before the pointers); MVN_OK for n_iter == 0.  Entries of idx outside
+ * [0, T) and of word_of_iter outside [0, n_words) are the caller's error: they are not checked.
+ * Results are bit-reproducible: the same inputs give the same bits on every run, and n iterations in one call equal n1 + n2
+ * iterations in two calls with the state carried over.
+ * A call of more than 8192 iterations is issued as several launches of at most 8192 on the stream (the arrival counter of the
+ * device-wide barrier is 32 bits wide); the result is that of one launch.
+ * mvn_lstm_train_lds_bytes: the dynamic LDS of the launch for words of length T (0 for an unsupported T); it grows by 160 bytes
+ * per step and is what sets MVN_LSTM_TRAIN_MAX_T.
+ * mvn_lstm_train_kernel_name: the launch of such a call (name is a host pointer). */
+#define MVN_LSTM_TRAIN_MAX_T 256
+size_t mvn_lstm_train_workspace_bytes(int32_t T);
+size_t mvn_lstm_train_lds_bytes(int32_t T);
+int mvn_lstm_train_f32(const float *y, int64_t y_ld, const int32_t *bits, int64_t bits_ld, int64_t n_words,
+                       const int32_t *word_of_iter, const int32_t *idx, int32_t M, int32_t n_iter, float *W_ih0, float *W_hh0,
+                       float *b_ih0, float *b_hh0, float *W_ih1, float *W_hh1, float *b_ih1, float *b_hh1, float *fc_W, float *fc_b,
+                       float *exp_avg, float *exp_avg_sq, int64_t step0, float lr, float beta1, float beta2, float eps,
+                       float *loss_out, void *workspace, size_t workspace_bytes, int32_t *status, int32_t T, mvn_stream_t stream);
+int mvn_lstm_train_kernel_name(int32_t T, int32_t M, char *name, int32_t name_len);
+
 #ifdef __cplusplus
 }
 #endif

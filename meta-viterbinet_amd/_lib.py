@@ -69,6 +69,11 @@ SIGNATURES = {
     "mvn_lstm_workspace_bytes": (ctypes.c_size_t, [_i64, _i32]),
     "mvn_lstm_decode_f32": (ctypes.c_int, [_vp, _i64] + [_vp] * 10 + [_vp, _i64, _vp, _vp, ctypes.c_size_t, _i64, _i32, _vp]),
     "mvn_lstm_decode_kernel_name": (ctypes.c_int, [_i64, _i32, ctypes.c_char_p, _i32]),
+    "mvn_lstm_train_workspace_bytes": (ctypes.c_size_t, [_i32]),
+    "mvn_lstm_train_lds_bytes": (ctypes.c_size_t, [_i32]),
+    "mvn_lstm_train_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _i32] + [_vp] * 12 +
+                           [_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp, _i32, _vp]),
+    "mvn_lstm_train_kernel_name": (ctypes.c_int, [_i32, _i32, ctypes.c_char_p, _i32]),
 }
 
 _lib = None

@@ -1148,6 +1148,7 @@ int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *man
 }
 
 #include "lstm.inc"
+#include "lstm_train.inc"
 
 }  // namespace
 
@@ -1760,6 +1761,62 @@ int mvn_lstm_decode_kernel_name(int64_t B, int32_t T, char *name, int32_t name_l
     if (B < 0 || T < 1) return MVN_E_DIMS;
     if (!name || name_len < 1) return MVN_E_NULL;
     snprintf(name, (size_t)name_len, "lstm_pack_kernel + lstm_decode_kernel<1> x %lld", (long long)((B + 15) / 16));
+    return MVN_OK;
+}
+
+size_t mvn_lstm_train_workspace_bytes(int32_t T) {
+    if (T < 1 || T > kLstmTrainMaxT) return 0;
+    return lt_ws_floats(T) * sizeof(float);
+}
+
+size_t mvn_lstm_train_lds_bytes(int32_t T) {
+    if (T < 1 || T > kLstmTrainMaxT) return 0;
+    return lstm_train_lds_bytes(T);
+}
+
+int mvn_lstm_train_f32(const float *y, int64_t y_ld, const int32_t *bits, int64_t bits_ld, int64_t n_words,
+                       const int32_t *word_of_iter, const int32_t *idx, int32_t M, int32_t n_iter, float *W_ih0, float *W_hh0,
+                       float *b_ih0, float *b_hh0, float *W_ih1, float *W_hh1, float *b_ih1, float *b_hh1, float *fc_W, float *fc_b,
+                       float *exp_avg, float *exp_avg_sq, int64_t step0, float lr, float beta1, float beta2, float eps,
+                       float *loss_out, void *workspace, size_t workspace_bytes, int32_t *status, int32_t T, mvn_stream_t stream) {
+    if (T < 1 || T > kLstmTrainMaxT || y_ld < T || bits_ld < T || n_iter < 0 || M < 0 || M > T || n_words < 1 || step0 < 0)
+        return MVN_E_DIMS;
+    if (n_iter == 0) return MVN_OK;
+    LstmTrainArgs a = {};
+    float *w[10] = {W_ih0, W_hh0, b_ih0, b_hh0, W_ih1, W_hh1, b_ih1, b_hh1, fc_W, fc_b};
+    for (int i = 0; i < 10; ++i) {
+        if (!w[i]) return MVN_E_NULL;
+        a.w[i] = w[i];
+    }
+    if (!y || !bits || !exp_avg || !exp_avg_sq || !workspace || (M > 0 && !idx)) return MVN_E_NULL;
+    if (workspace_bytes < lt_ws_floats(T) * sizeof(float) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
+    a.y = y;
+    a.y_ld = y_ld;
+    a.bits = bits;
+    a.bits_ld = bits_ld;
+    a.word_of_iter = word_of_iter;
+    a.idx = M > 0 ? idx : nullptr;
+    a.M = M;
+    a.n_iter = n_iter;
+    a.m = exp_avg;
+    a.v = exp_avg_sq;
+    a.step0 = step0;
+    a.lr = lr;
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.eps = eps;
+    a.loss_out = loss_out;
+    a.ws = (float *)workspace;
+    a.ws_bytes = (unsigned)(lt_ws_floats(T) * sizeof(float));
+    a.status = status;
+    a.T = T;
+    return launch_lstm_train(a, (hipStream_t)stream);
+}
+
+int mvn_lstm_train_kernel_name(int32_t T, int32_t M, char *name, int32_t name_len) {
+    if (T < 1 || T > kLstmTrainMaxT || M < 0 || M > T) return MVN_E_DIMS;
+    if (!name || name_len < 1) return MVN_E_NULL;
+    snprintf(name, (size_t)name_len, "lstm_train_kernel x %d (%s)", kLtGroups, M > 0 ? "minibatch" : "whole word");
     return MVN_OK;
 }
 

@@ -244,11 +244,18 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
 
-    from .lstm import LSTMDetector, MetaLSTMDetector
+    from .lstm import LSTMDetector, LSTMOnlineTrainer, MetaLSTMDetector
 
-    if (self_supervised or online_meta) and isinstance(detector, (LSTMDetector, MetaLSTMDetector)):
-        raise ValueError("eval_by_word: online training / meta-learning of the LSTM detector is not built (lstm_trainer.py, "
-                         "meta_lstm_trainer.py); run it without self_supervised and online_meta")
+    if isinstance(detector, (LSTMDetector, MetaLSTMDetector)):
+        if online_meta:
+            raise ValueError("eval_by_word: meta-learning of the LSTM detector is not built (meta_lstm_trainer.py); run it without "
+                             "online_meta")
+        if (self_supervised or online_trainer is not None) and not (isinstance(detector, LSTMDetector)
+                                                                    and isinstance(online_trainer, LSTMOnlineTrainer)):
+            raise ValueError("eval_by_word: online training of an LSTMDetector needs online_trainer=LSTMOnlineTrainer(detector) "
+                             "(lstm_trainer.py, meta_lstm_trainer.py)")
+    elif isinstance(online_trainer, LSTMOnlineTrainer):
+        raise ValueError("eval_by_word: an LSTMOnlineTrainer trains an LSTMDetector")
     N = tx.shape[0]
     ser_by_word = np.zeros(N)
     K = tx.shape[1]
@@ -297,7 +304,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     meta_step = None  # meta.GraphedMetaStep, built at the first meta update (graphed_meta and a CUDA detector)
     graphed_meta = graphed_meta and rx.is_cuda and (online_trainer is None or online_trainer.optimizer_type == "Adam")  # captured Adam update
     # mvn_vnet_maml_train_f32: the LDS holds 4 parameter vectors (n_states <= 32); the kernel's optimizer is Adam
-    hip_meta = (hip_meta and rx.is_cuda and detector.n_states <= 32 and online_trainer is not None
+    hip_meta = (hip_meta and online_meta and rx.is_cuda and detector.n_states <= 32 and online_trainer is not None
                 and online_trainer.optimizer_type == "Adam" and online_trainer.use_kernel)
     support_idx = torch.arange(-window_size - 1, -1, device=rx.device).long()  # :288
     query_idx = -1 * torch.ones(1, device=rx.device).long()

@@ -1,12 +1,16 @@
 """LSTM detectors: same constructors, forward() signatures, constants and state_dict keys as
 python_code/detectors/LSTM/lstm_detector.py and detectors/META_LSTM/meta_lstm_detector.py.  Phase 'val' runs on the MI355X through
 libmvn_hip.so (mvn_lstm_decode_f32: window, both layers, fc and argmax in one kernel); every other phase returns the logits from
-torch autograd.  LSTM online training and meta-learning are not built: the harness's update branches refuse these detectors."""
+torch autograd.  LSTMOnlineTrainer trains an LSTMDetector -- online on one word (lstm_trainer.py:42-53, meta_lstm_trainer.py:48-60)
+or jointly, one word per step (trainer.py:470-479) -- with every iteration of a call inside one launch of mvn_lstm_train_f32
+(forward, CrossEntropy, backward through time and the optimizer step; csrc/lstm_train.inc).  LSTM meta-learning (MAML through the
+unrolled cell) is not built: harness.eval_by_word refuses online_meta with these detectors."""
 import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
 from . import _lib
+from .online import OnlineTrainer
 
 INPUT_SIZE = 4  # lstm_detector.py:6-10
 HIDDEN_SIZE = 256
@@ -108,3 +112,128 @@ class MetaLSTMDetector(nn.Module):
             top.append(inp)
         out = torch.stack(top, dim=1).reshape(-1, HIDDEN_SIZE)
         return F.linear(out, var[-2], var[-1]).reshape(B, T, N_CLASSES)
+
+
+TRAIN_MAX_T = 256  # MVN_LSTM_TRAIN_MAX_T (include/mvn.h): longer words take the autograd route
+
+
+class LSTMOnlineTrainer(OnlineTrainer):
+    """The optimizer state (exp_avg, exp_avg_sq, step) of an LSTMDetector's ten parameters, like the optimizer
+    deep_learning_setup() creates (trainer.py:163-175), and the training loops of LSTMTrainer / MetaLSTMTrainer on it.  Same duck
+    type as OnlineTrainer (params, exp_avg, exp_avg_sq, step, sync_words / status / check_status, reset_state, select_batches,
+    kernel_optimizer_args, optimizer_type, use_kernel).  use_kernel=True (the default) runs mvn_lstm_train_f32; use_kernel=False, a CPU detector or a word longer than TRAIN_MAX_T takes stock autograd on the same
+    state: the cross-check of the kernel and the CPU route."""
+
+    def __init__(self, detector, lr: float = 0.001, betas=(0.9, 0.999), eps: float = 1e-8, train_minibatch_size: int = 32,
+                 use_kernel: bool = True, optimizer_type: str = "Adam"):
+        # use_kernel=True is the default because the kernel route is the faster one (profiles/lstm_train_time.txt: 1.10 ms against
+        # 14.8 ms per iteration at T = 136; DESIGN.md 5.10)
+        if optimizer_type not in ("Adam", "RMSprop", "SGD"):  # deep_learning_setup (trainer.py:163-175)
+            raise NotImplementedError("No such optimizer implemented!!!")
+        if not isinstance(detector, LSTMDetector):
+            raise ValueError("LSTMOnlineTrainer trains an LSTMDetector")
+        self.detector = detector
+        self.optimizer_type = optimizer_type
+        self.use_kernel = use_kernel
+        self.memory_length = None
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.train_minibatch_size = train_minibatch_size
+        self.params = detector._params()
+        if [tuple(p.shape) for p in self.params] != PARAM_SHAPES:
+            raise ValueError(f"LSTM parameter shapes {[tuple(p.shape) for p in self.params]} != {PARAM_SHAPES}")
+        dev = self.params[0].device
+        n = sum(p.numel() for p in self.params)
+        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.step = 0
+        self.sync_words = torch.zeros(2, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
+        self.status = self.sync_words[1:2] if dev.type == "cuda" else None
+        self._unchecked = False
+
+    def maml_training(self, *args, **kwargs):
+        raise NotImplementedError("LSTM meta-learning is not built")
+
+    def kernel_route(self, T: int) -> bool:
+        """Does a call on words of length T run mvn_lstm_train_f32?"""
+        return bool(self.use_kernel and self.params[0].is_cuda and 1 <= T <= TRAIN_MAX_T)
+
+    def _workspace(self, T: int, dev) -> torch.Tensor:
+        ws = getattr(self, "_ws", None)
+        need = int(_lib.load().mvn_lstm_train_workspace_bytes(T))
+        if ws is None or ws.device != dev or ws.numel() < need:
+            ws = self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    def online_training(self, tx: torch.Tensor, rx: torch.Tensor, iterations: int = 200, batch_idx: torch.Tensor = None,
+                        full_word: bool = False, return_loss: bool = False, labels: torch.Tensor = None):
+        """`iterations` steps on ONE word: tx [1, T] its bits (the labels), rx [1, T] the received word.  full_word=False is
+        LSTMTrainer's form (lstm_trainer.py:30-53: the loss over train_minibatch_size positions per iteration, batch_idx
+        [iterations, M] or drawn by select_batches); full_word=True MetaLSTMTrainer's (meta_lstm_trainer.py:38-60: the whole word).
+        labels is accepted for OnlineTrainer's signature and unused (the labels are tx)."""
+        T = rx.reshape(-1).numel()
+        idx = None
+        if not full_word:
+            idx = self.select_batches(T, iterations) if batch_idx is None else batch_idx
+            if idx.dim() != 2 or idx.shape[0] != iterations:
+                raise ValueError("batch_idx must be [iterations, M]")
+        return self._train(tx.reshape(1, T), rx.reshape(1, T), None, iterations, idx, return_loss)
+
+    def train_words(self, tx_words: torch.Tensor, rx_words: torch.Tensor, batch_idx: torch.Tensor = None, full_word: bool = False,
+                    return_loss: bool = False):
+        """One step per row of tx_words / rx_words [n, T], in row order: the inner loop of Trainer.train() (trainer.py:476-479)."""
+        n, T = rx_words.shape
+        idx = None
+        if not full_word:
+            idx = self.select_batches(T, n) if batch_idx is None else batch_idx
+            if idx.dim() != 2 or idx.shape[0] != n:
+                raise ValueError("batch_idx must be [n_words, M]")
+        return self._train(tx_words, rx_words, torch.arange(n, dtype=torch.int32), n, idx, return_loss)
+
+    def _train(self, tx, rx, word_of_iter, iterations, idx, return_loss):
+        p = self.params
+        dev = p[0].device
+        T = rx.shape[1]
+        if not self.kernel_route(T):
+            return self._train_autograd(tx, rx, word_of_iter, iterations, idx, return_loss)
+        _lib.require_gpu_tensor(rx, "rx")
+        y = _lib.f32c(rx)
+        bits = tx.detach().to(device=dev, dtype=torch.int32).contiguous()
+        M = 0
+        if idx is not None:
+            idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+            M = idx.shape[1]
+        woi = None if word_of_iter is None else word_of_iter.to(device=dev, dtype=torch.int32).contiguous()
+        for t in p:
+            if not t.data.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("LSTM parameters must be contiguous fp32")
+        loss = torch.empty(iterations, dtype=torch.float32, device=dev) if return_loss else None
+        ws = self._workspace(T, dev)
+        b1, b2, eps = self.kernel_optimizer_args()
+        with _lib.on_device(dev):
+            rc = _lib.load().mvn_lstm_train_f32(_lib.ptr(y), T, _lib.ptr(bits), T, y.shape[0], _lib.ptr(woi), _lib.ptr(idx), M, iterations,
+                                                *[_lib.ptr(t.data) for t in p], _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                                                self.step, self.lr, b1, b2, eps, _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
+                                                _lib.ptr(self.status), T, _lib.current_stream(dev))
+        _lib.check(rc, "mvn_lstm_train_f32")
+        self._unchecked = True
+        self.step += iterations
+        return loss
+
+    def _train_autograd(self, tx, rx, word_of_iter, iterations, idx, return_loss):
+        """The same loop on stock PyTorch autograd (run_train_loop, trainer.py:492-505): LSTMDetector(rx, 'train'), CrossEntropy
+        over the selected positions, optimizer_step on the shared exp_avg / exp_avg_sq / step."""
+        p = self.params
+        dev = p[0].device
+        y = rx.detach().to(device=dev, dtype=p[0].dtype)
+        lab = tx.detach().to(dev).long()
+        if idx is not None:
+            idx = idx.to(dev).long()
+        losses = []
+        for it in range(iterations):
+            w = 0 if word_of_iter is None else int(word_of_iter[it])
+            logits = self.detector(y[w:w + 1], "train").reshape(-1, N_CLASSES)
+            loss = F.cross_entropy(logits, lab[w]) if idx is None else F.cross_entropy(logits[idx[it]], lab[w][idx[it]])
+            self.optimizer_step(torch.autograd.grad(loss, p))
+            if return_loss:
+                losses.append(loss.detach())
+        return torch.stack(losses).to(torch.float32) if return_loss else None
