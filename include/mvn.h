@@ -470,7 +470,9 @@ int mvn_lstm_decode_kernel_name(int64_t B, int32_t T, char *name, int32_t name_l
  * 1 <= T <= 256 (MVN_LSTM_TRAIN_MAX_T: the saved activations of all T steps share the LDS with the weight slices); the launch
  * uses 64 workgroups and returns MVN_E_DEVICE on a device with fewer CUs.  MVN_E_DIMS for T out of range, a row stride < T,
  * n_iter < 0, M < 0, M > T, n_words < 1 or step0 < 0 (checked before the pointers); MVN_OK for n_iter == 0.  Entries of idx outside
- * [0, T) and of word_of_iter outside [0, n_words) are the caller's error: they are not checked.
+ * [0, T) and of word_of_iter outside [0, n_words) are the caller's error: they are not checked (the call cannot see device memory).  A
+ * position outside [0, T) counts for nothing while the mean still divides by M -- where torch would raise, the loss and the
+ * gradient come out too small by that share; a word outside [0, n_words) is read out of bounds.
  * Results are bit-reproducible: the same inputs give the same bits on every run, and n iterations in one call equal n1 + n2
  * iterations in two calls with the state carried over.
  * A call of more than 8192 iterations is issued as several launches of at most 8192 on the stream (the arrival counter of the

@@ -6,7 +6,10 @@ autograd route (use_kernel=False, the CPU route) against torch autograd + torch.
 Tolerance (the project's training tests, tests/test_gpu_parity.py): parameters |d| <= 2e-5 + 1e-3 |w|, per-iteration loss
 rtol 2e-4 / atol 1e-6, against the float64 referee started from identical weights and draws.  In the Adam cases more than 90 % of
 the parameters move by more than ten times that bound, so it is a sensitive one; SGD's small updates are checked relative to the
-update itself as well."""
+update itself as well.  What it does not see -- Adam and RMSprop divide the gradient's scale out, so a gradient short of a time step
+or wrong by a factor gives nearly the same update; one wrong row hides in a tensor's norm; no draw here repeats a position -- is
+held element by element in tests/lstm_grad_cases.py (tests/test_lstm_grad_host.py, tests/test_gpu_lstm_grad.py): the gradient itself,
+read out of Adam's first moment, at T = 1 ... 256."""
 import ctypes
 import os
 import re
