@@ -490,6 +490,35 @@ int mvn_lstm_train_f32(const float *y, int64_t y_ld, const int32_t *bits, int64_
                        float *loss_out, void *workspace, size_t workspace_bytes, int32_t *status, int32_t T, mvn_stream_t stream);
 int mvn_lstm_train_kernel_name(int32_t T, int32_t M, char *name, int32_t name_len);
 
+/* Online meta-learning of the same network in one launch (lstm_train.inc, the meta-learning form of the training kernel): n_steps x
+ * Trainer.meta_train_loop (trainers/trainer.py:425-453) as MetaLSTMTrainer runs it from eval_by_word (:331-343), FIRST ORDER ONLY
+ * (MAML=False, create_graph=False) and with ONE support word per step (window_size = 1).  Step k: forward, CrossEntropyLoss(mean) over
+ * the whole word and backward through time on word support_idx[k] at the parameters theta; the fast weights
+ * theta' = fl(theta - fl(meta_lr * g)); the same on word query_idx[k] at theta'; the query gradient -- torch.autograd.grad(loss_query,
+ * params) with create_graph=False -- drives one optimizer step on THETA.  The second-order term (MAML=True) and several support
+ * words are not built on the device: callers take torch autograd for them.
+ *   rx_words [n_words, T] (row stride rx_ld), bits int32 [n_words, T] in {0,1} (row stride bits_ld); support_idx, query_idx: device
+ *   int32 [n_steps], entries in [0, n_words) (not checked: the call cannot see device memory; a word outside is read out of bounds).
+ *   The ten tensors, exp_avg, exp_avg_sq, step0, lr, beta1, beta2, eps, status: as mvn_lstm_train_f32 (Adam, RMSprop or SGD by the
+ *   beta1 tag); step k is optimizer step step0 + k + 1.  loss_out [n_steps] or NULL: the query losses.
+ *   workspace: mvn_lstm_maml_workspace_bytes(T) bytes of device memory, 16-byte aligned, private to the call while it runs: the
+ *   training workspace and behind it the fast-weight image (theta' of W_hh0, W_ih1, W_hh1 and the fc layer, 3.15 MB).
+ * 1 <= T <= MVN_LSTM_TRAIN_MAX_T; 64 workgroups, MVN_E_DEVICE on a device with fewer CUs.  MVN_E_DIMS for T out of range, a row stride
+ * < T, n_steps < 0, n_words < 1 or step0 < 0 (checked before the pointers); MVN_OK for n_steps == 0; MVN_E_NULL for a missing pointer
+ * (loss_out and status may be NULL); MVN_E_WORKSPACE for a small or unaligned workspace.
+ * With meta_lr = 0 a step is bit for bit one whole-word iteration of mvn_lstm_train_f32 on the query word.  Results are
+ * bit-reproducible and n steps in one call equal n1 + n2 steps in two.  A call of more than 4096 steps is issued as several launches
+ * on the stream (two passes of the training loop per step against the 32-bit arrival counter).
+ * mvn_lstm_maml_kernel_name: the launch of such a call (name is a host pointer). */
+size_t mvn_lstm_maml_workspace_bytes(int32_t T);
+int mvn_lstm_maml_train_f32(const float *rx_words, int64_t rx_ld, const int32_t *bits, int64_t bits_ld, int64_t n_words,
+                            const int32_t *support_idx, const int32_t *query_idx, int32_t n_steps, float *W_ih0, float *W_hh0,
+                            float *b_ih0, float *b_hh0, float *W_ih1, float *W_hh1, float *b_ih1, float *b_hh1, float *fc_W,
+                            float *fc_b, float *exp_avg, float *exp_avg_sq, int64_t step0, float meta_lr, float lr, float beta1,
+                            float beta2, float eps, float *loss_out, void *workspace, size_t workspace_bytes, int32_t *status,
+                            int32_t T, mvn_stream_t stream);
+int mvn_lstm_maml_kernel_name(int32_t T, char *name, int32_t name_len);
+
 #ifdef __cplusplus
 }
 #endif

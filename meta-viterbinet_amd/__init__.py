@@ -4,7 +4,7 @@ from . import _lib
 from .channel import BPSKModulator, ReferenceWordStream, estimate_channel, generate_words, transmit
 from .detectors import HIDDEN1_SIZE, HIDDEN2_SIZE, META_VNETDetector, VADetector, VNETDetector
 from .ecc import rs_decode, rs_encode
-from .lstm import LSTMDetector, LSTMOnlineTrainer, MetaLSTMDetector
+from .lstm import LSTMDetector, LSTMMetaTrainer, LSTMOnlineTrainer, MetaLSTMDetector
 from .harness import (data_indices, detect_by_word, eval_by_word, eval_counters, replica_eval, shard_range, sharded_eval,
                       single_eval_at_point, synthetic_words, va_monte_carlo)
 from .meta import GraphedMetaStep, copy_model, meta_train_loop
@@ -14,7 +14,7 @@ from .metrics import calculate_error_rates, count_errors, rates_from_counters
 from .trellis import acs_block, acs_sweep, acs_sweep_survivors, calculate_states, create_transition_table, traceback
 
 __all__ = [
-    "VADetector", "VNETDetector", "META_VNETDetector", "HIDDEN1_SIZE", "HIDDEN2_SIZE", "LSTMDetector", "MetaLSTMDetector", "LSTMOnlineTrainer",
+    "VADetector", "VNETDetector", "META_VNETDetector", "HIDDEN1_SIZE", "HIDDEN2_SIZE", "LSTMDetector", "MetaLSTMDetector", "LSTMOnlineTrainer", "LSTMMetaTrainer",
     "create_transition_table", "acs_block", "acs_sweep", "acs_sweep_survivors", "traceback", "calculate_states",
     "calculate_error_rates", "count_errors", "rates_from_counters",
     "estimate_channel", "BPSKModulator", "transmit", "generate_words", "ReferenceWordStream", "rs_encode", "rs_decode", "OnlineTrainer", "meta_train_loop", "GraphedMetaStep", "copy_model",

@@ -74,6 +74,10 @@ SIGNATURES = {
     "mvn_lstm_train_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _i32] + [_vp] * 12 +
                            [_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp, _i32, _vp]),
     "mvn_lstm_train_kernel_name": (ctypes.c_int, [_i32, _i32, ctypes.c_char_p, _i32]),
+    "mvn_lstm_maml_workspace_bytes": (ctypes.c_size_t, [_i32]),
+    "mvn_lstm_maml_train_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i32] + [_vp] * 12 +
+                                [_i64] + [ctypes.c_float] * 5 + [_vp, _vp, ctypes.c_size_t, _vp, _i32, _vp]),
+    "mvn_lstm_maml_kernel_name": (ctypes.c_int, [_i32, ctypes.c_char_p, _i32]),
 }
 
 _lib = None

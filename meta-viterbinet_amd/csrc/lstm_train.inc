@@ -23,6 +23,8 @@
 // step number (pow_int below), n iterations in one call equal n1 + n2 in two.
 // A wait that is abandoned (spin limit, train_groups.inc) is sticky: every workgroup leaves its loops, writes NaN over the
 // parameters it owns and sets *status = 1.
+// lstm_maml_kernel is the same body run twice per step (support pass, query pass): first-order online meta-learning, see
+// LstmMetaArgs below.
 constexpr int kLtGroups = 64, kLtThreads = 256, kLtU = kLstmH / kLtGroups, kLtR = 4 * kLtU;
 constexpr int kLstmTrainMaxT = 256;       // LDS: 40 T floats of saved activations beside 96 KB of weights
 constexpr int kLstmTrainMaxIter = 8192;   // iterations per launch (the arrival counter is 32 bits wide)
@@ -100,7 +102,24 @@ __device__ __forceinline__ float lt_reduce16(float v) {  // sum over the 16 lane
     return v;
 }
 
-__global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainArgs a) {
+// Online meta-learning (first-order MAML, Trainer.meta_train_loop with MAML=False, trainer.py:425-453) on the same sweeps: META runs
+// the loop body TWICE per step.  The support pass (word support_of_step[k]) ends in theta' = fl(theta - meta_lr g_s) instead of the
+// optimizer step: theta' replaces the LDS working copies and goes, for the three big matrices and the fc layer, to a fast-weight
+// image behind the training workspace, from which every workgroup re-reads its column copies and the fc layer after the pass's
+// closing barrier; a.w[] and the moments are not touched.  The query pass (word word_of_iter[k]) runs at theta', its loss is
+// loss_out[k], and its gradient -- the first-order meta-gradient -- drives adam1 on THETA, which the owner reads back from a.w[].
+// One support word, first order only: the second-order term needs a tangent copy of the weights that LDS has no room for.
+struct LstmMetaArgs : LstmTrainArgs {
+    const int *support_of_step;
+    float meta_lr;
+};
+// the fast-weight image, in floats from its base: W_hh0, W_ih1, W_hh1, fc weight, fc bias
+constexpr size_t kLtFastHh0 = 0, kLtFastIh1 = (size_t)kLstmGates * kLstmH, kLtFastHh1 = 2 * kLtFastIh1, kLtFastFc = 3 * kLtFastIh1;
+constexpr size_t kLtFastFcb = kLtFastFc + 2 * kLstmH, kLtFastFloats = kLtFastFcb + 4;
+__host__ __device__ constexpr size_t lt_maml_ws_floats(int T) { return lt_ws_floats(T) + kLtFastFloats; }
+
+template <bool META, class Args>
+__device__ __forceinline__ void lstm_train_body(const Args a) {  // (by value: a reference costs lstm_train_kernel three VGPRs)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int T = a.T, Tp = (T + 3) & ~3, M = a.M;
     const LtLds L(T);
@@ -113,6 +132,7 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
     const SlotIO io(a.ws, a.ws_bytes);  // same_xcd stays false: write-through stores, sc1 loads
     const SlotIO mhh0(a.w[1], kLstmGates * kLstmH * 4), mih1(a.w[4], kLstmGates * kLstmH * 4), mhh1(a.w[5], kLstmGates * kLstmH * 4);
     const SlotIO fcio(a.w[8], 2 * kLstmH * 4), fcbio(a.w[9], 8);
+    const SlotIO fio(META ? a.ws + lt_ws_floats(T) : a.ws, (unsigned)(kLtFastFloats * 4));  // META only: the fast-weight image
     const size_t H0 = lt_ws_hist(), H1 = H0 + (size_t)T * kLstmH, DG = lt_ws_dg(T);
     auto row_of = [&](int r) { return 256 * (r >> 2) + kLtU * g + (r & 3); };  // local row -> gate row of the matrices
     auto sv = [&](int l, int uu, int q, int t) -> float & { return saved[((l * kLtU + uu) * 5 + q) * Tp + t]; };
@@ -133,10 +153,11 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
         bias[3 * kLtR + tid] = a.w[7][n];
     }
     // column copies wcol[m][kk][n]: m = 0 W_hh1, 1 W_ih1, 2 W_hh0; and the fc layer
-    auto read_shared = [&]() {
+    auto read_from = [&](const SlotIO &shh1, const SlotIO &sih1, const SlotIO &shh0, const SlotIO &sfc, const SlotIO &sfcb, size_t ohh1,
+                         size_t oih1, size_t ohh0, size_t ofc, size_t ofcb) {
         for (int n = tid; n < kLstmGates; n += kLtThreads) {
             const size_t at = (size_t)n * kLstmH + kLtU * g;
-            const float4 v[3] = {mhh1.load4(at), mih1.load4(at), mhh0.load4(at)};
+            const float4 v[3] = {shh1.load4(ohh1 + at), sih1.load4(oih1 + at), shh0.load4(ohh0 + at)};
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 float *dst = wcol + (m * kLtU) * kLstmGates + n;
@@ -146,9 +167,11 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
                 dst[3 * kLstmGates] = v[m].w;
             }
         }
-        if (tid < 2 * kLstmH / 4) reinterpret_cast<float4 *>(fcw)[tid] = fcio.load4(4 * (size_t)tid);
-        if (tid < 2) fcw[2 * kLstmH + tid] = fcbio.load1(tid);
+        if (tid < 2 * kLstmH / 4) reinterpret_cast<float4 *>(fcw)[tid] = sfc.load4(ofc + 4 * (size_t)tid);
+        if (tid < 2) fcw[2 * kLstmH + tid] = sfcb.load1(ofcb + tid);
     };
+    auto read_shared = [&]() { read_from(mhh1, mih1, mhh0, fcio, fcbio, 0, 0, 0, 0, 0); };
+    auto read_fast = [&]() { read_from(fio, fio, fio, fio, fio, kLtFastHh1, kLtFastIh1, kLtFastHh0, kLtFastFc, kLtFastFcb); };
     read_shared();
     if (tid < 3) yw[tid] = kLstmPad;
     __syncthreads();
@@ -156,8 +179,13 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
     unsigned epoch = 0;
     bool good = true;
     const int sub = tid & 15, grp = tid >> 4;
-    for (int it = 0; it < a.n_iter && good; ++it) {
-        const long long word = a.word_of_iter ? a.word_of_iter[it] : 0;
+    const int n_pass = META ? 2 * a.n_iter : a.n_iter;  // META: support pass, query pass of step k = it / 2
+    for (int it = 0; it < n_pass && good; ++it) {
+        const bool query = !META || (it & 1);
+        const int k = META ? it >> 1 : it;
+        long long word;
+        if constexpr (META) word = query ? a.word_of_iter[k] : a.support_of_step[k];
+        else word = a.word_of_iter ? a.word_of_iter[it] : 0;
         if (tid < T) {
             yw[3 + tid] = a.y[word * a.y_ld + tid];
             lab[tid] = a.bits[word * a.bits_ld + tid];
@@ -245,11 +273,11 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
             dl[2 * tid + 1] = (e1 / se - (lb ? 1.0f : 0.0f)) * scale;
         }
         __syncthreads();
-        if (g == 0 && tid < 64 && a.loss_out) {  // sum_t scale_t nll_t: lane-strided partial sums, then a fixed tree
+        if (g == 0 && tid < 64 && a.loss_out && query) {  // sum_t scale_t nll_t: lane-strided partial sums, then a fixed tree
             float sum = 0.0f;
             for (int t = tid; t < T; t += 64) sum += cnt[t] * nll[t];
             for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
-            if (tid == 0) a.loss_out[it] = sum;
+            if (tid == 0) a.loss_out[k] = sum;
         }
         // ---- backward through time: step s runs layer 1 at t = s and layer 0 at t = s + 1
         float carry = 0.0f;  // threads < 8: dc(t + 1) f(t + 1) of this thread's (layer, unit)
@@ -308,16 +336,30 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
         }
         if (!good) break;
         // ---- weight gradients of the owned rows (thread k = column k, t ascending) and the optimizer step
-        const long long step = a.step0 + it + 1;
+        const long long step = a.step0 + k + 1;
         const float step_size = train_step_size(a.lr, a.beta1, a.beta1 >= 0.0f ? pow_int((double)a.beta1, step) : 0.0);
         const float inv_sqrt_bc2 = a.beta1 >= 0.0f ? (float)(1.0 / sqrt(1.0 - pow_int((double)a.beta2, step))) : 1.0f;
-        auto update = [&](float *pp, size_t e, float gr) {  // one parameter (global, element e of the flat moments); returns via *pp
-            float p = *pp, m = a.m[e], v = a.v[e];
+        // one parameter (global, element e of the flat moments); returns via *pp.  META: the support pass takes the inner step
+        // p - meta_lr g (one rounding each, like torch) on the working copy; the query pass steps theta, which theta() reads back
+        auto update = [&](float *pp, size_t e, float gr, auto theta) {
+            if constexpr (META) {
+                if (!query) {
+                    const float fast = __fsub_rn(*pp, __fmul_rn(a.meta_lr, gr));
+                    *pp = fast;
+                    return fast;
+                }
+            }
+            float p = META ? theta() : *pp, m = a.m[e], v = a.v[e];
             adam1(p, m, v, gr, a.beta1, a.beta2, a.eps, step_size, inv_sqrt_bc2);
             if (a.beta1 >= 0.0f) a.m[e] = m;
             if (a.beta1 > -1.5f) a.v[e] = v;
             *pp = p;
             return p;
+        };
+        // a shared parameter's new value: write-through to its tensor, or (META, support pass) to the fast-weight image
+        auto put = [&](const SlotIO &real, size_t fast_at, size_t e, float v) {
+            if (META && !query) fio.store1(fast_at + e, v);
+            else real.store1(e, v);
         };
         {
             float acc0[kLtR], acc1[kLtR], acc2[kLtR], fc0 = 0.0f, fc1 = 0.0f;
@@ -343,13 +385,13 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
             for (int r = 0; r < kLtR; ++r) {
                 const size_t e = (size_t)row_of(r) * kLstmH + tid;
                 float *w0 = wrow + (0 * kLtR + r) * kLstmH + tid, *w1 = w0 + kLtR * kLstmH, *w2 = w1 + kLtR * kLstmH;
-                mhh0.store1(e, update(w0, kLtOff[1] + e, acc0[r]));
-                mih1.store1(e, update(w1, kLtOff[4] + e, acc1[r]));
-                mhh1.store1(e, update(w2, kLtOff[5] + e, acc2[r]));
+                put(mhh0, kLtFastHh0, e, update(w0, kLtOff[1] + e, acc0[r], [&] { return mhh0.load1(e); }));
+                put(mih1, kLtFastIh1, e, update(w1, kLtOff[4] + e, acc1[r], [&] { return mih1.load1(e); }));
+                put(mhh1, kLtFastHh1, e, update(w2, kLtOff[5] + e, acc2[r], [&] { return mhh1.load1(e); }));
             }
             if ((tid >> 2) == g) {  // the fc columns of the owned units
-                fcio.store1(tid, update(fcw + tid, kLtOff[8] + tid, fc0));
-                fcio.store1(kLstmH + tid, update(fcw + kLstmH + tid, kLtOff[8] + kLstmH + tid, fc1));
+                put(fcio, kLtFastFc, tid, update(fcw + tid, kLtOff[8] + tid, fc0, [&] { return fcio.load1(tid); }));
+                put(fcio, kLtFastFc, kLstmH + tid, update(fcw + kLstmH + tid, kLtOff[8] + kLstmH + tid, fc1, [&] { return fcio.load1(kLstmH + tid); }));
             }
         }
         if (tid < kLtR * kLstmIn) {  // W_ih0[row][j]
@@ -357,24 +399,30 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
             float acc = 0.0f;
             for (int t = 0; t < T; ++t) acc = fmaf(sv(0, r & 3, r >> 2, t), yw[t + j], acc);
             const size_t e = (size_t)row_of(r) * kLstmIn + j;
-            a.w[0][e] = update(wih0 + tid, kLtOff[0] + e, acc);
+            const float p = update(wih0 + tid, kLtOff[0] + e, acc, [&] { return a.w[0][e]; });  // (owner-only: its own plain store)
+            if (query) a.w[0][e] = p;
         } else if (tid < kLtR * kLstmIn + 2 * kLtR) {  // b_ih and b_hh of a layer share one gradient
             const int l = (tid - kLtR * kLstmIn) >> 4, r = tid & 15;
             float acc = 0.0f;
             for (int t = 0; t < T; ++t) acc += sv(l, r & 3, r >> 2, t);
             const int n = row_of(r);
             float *bi = l ? a.w[6] : a.w[2], *bh = l ? a.w[7] : a.w[3];
-            bi[n] = update(bias + (2 * l) * kLtR + r, (l ? kLtOff[6] : kLtOff[2]) + n, acc);
-            bh[n] = update(bias + (2 * l + 1) * kLtR + r, (l ? kLtOff[7] : kLtOff[3]) + n, acc);
+            const float pi = update(bias + (2 * l) * kLtR + r, (l ? kLtOff[6] : kLtOff[2]) + n, acc, [&] { return bi[n]; });
+            const float ph = update(bias + (2 * l + 1) * kLtR + r, (l ? kLtOff[7] : kLtOff[3]) + n, acc, [&] { return bh[n]; });
+            if (query) {
+                bi[n] = pi;
+                bh[n] = ph;
+            }
         } else if (g == 0 && tid < kLtR * kLstmIn + 2 * kLtR + 2) {  // fc bias
             const int c = tid - (kLtR * kLstmIn + 2 * kLtR);
             float acc = 0.0f;
             for (int t = 0; t < T; ++t) acc += dl[2 * t + c];
-            fcbio.store1(c, update(fcw + 2 * kLstmH + c, kLtOff[9] + c, acc));
+            put(fcbio, kLtFastFcb, c, update(fcw + 2 * kLstmH + c, kLtOff[9] + c, acc, [&] { return fcbio.load1(c); }));
         }
         good = groups_barrier(gs, kLtGroups, epoch, a.spin_limit) && good;
-        if (good && it + 1 < a.n_iter) {
-            read_shared();
+        if (good && it + 1 < n_pass) {
+            if (META && !query) read_fast();
+            else read_shared();
             __syncthreads();
         }
     }
@@ -397,6 +445,9 @@ __global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainA
     if (tid == 0 && a.status) *a.status = 1;
 }
 
+__global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainArgs a) { lstm_train_body<false>(a); }
+__global__ __launch_bounds__(kLtThreads) void lstm_maml_kernel(const LstmMetaArgs a) { lstm_train_body<true>(a); }
+
 // n_iter iterations in launches of at most kLstmTrainMaxIter; the arrival counter is zeroed in front of each
 int launch_lstm_train(LstmTrainArgs a, hipStream_t st) {
     if (current_device_cus() < kLtGroups) return MVN_E_DEVICE;  // one workgroup per CU, all resident at once
@@ -415,6 +466,28 @@ int launch_lstm_train(LstmTrainArgs a, hipStream_t st) {
         if (a.idx) b.idx = a.idx + (long long)done * a.M;
         if (a.loss_out) b.loss_out = a.loss_out + done;
         hipLaunchKernelGGL(lstm_train_kernel, dim3(kLtGroups), dim3(kLtThreads), lds, st, b);
+        if (int rc = (int)hipGetLastError()) return rc;
+    }
+    return MVN_OK;
+}
+
+// n_steps meta-learning steps in launches of at most kLstmTrainMaxIter / 2 (two passes of the loop body per step)
+int launch_lstm_maml(LstmMetaArgs a, hipStream_t st) {
+    if (current_device_cus() < kLtGroups) return MVN_E_DEVICE;
+    const size_t lds = lstm_train_lds_bytes(a.T);
+    if (int e = ensure_dynamic_lds((const void *)lstm_maml_kernel, lstm_train_lds_bytes(kLstmTrainMaxT))) return e;
+    a.spin_limit = group_spin_limit();
+    const int total = a.n_iter, per = kLstmTrainMaxIter / 2;
+    for (int done = 0; done < total; done += per) {
+        hipError_t e = hipMemsetAsync(a.ws, 0, sizeof(GroupSync), st);
+        if (e != hipSuccess) return (int)e;
+        LstmMetaArgs b = a;
+        b.n_iter = std::min(per, total - done);
+        b.step0 = a.step0 + done;
+        b.word_of_iter = a.word_of_iter + done;
+        b.support_of_step = a.support_of_step + done;
+        if (a.loss_out) b.loss_out = a.loss_out + done;
+        hipLaunchKernelGGL(lstm_maml_kernel, dim3(kLtGroups), dim3(kLtThreads), lds, st, b);
         if (int rc = (int)hipGetLastError()) return rc;
     }
     return MVN_OK;

@@ -1820,4 +1820,55 @@ int mvn_lstm_train_kernel_name(int32_t T, int32_t M, char *name, int32_t name_le
     return MVN_OK;
 }
 
+size_t mvn_lstm_maml_workspace_bytes(int32_t T) {
+    if (T < 1 || T > kLstmTrainMaxT) return 0;
+    return lt_maml_ws_floats(T) * sizeof(float);
+}
+
+int mvn_lstm_maml_train_f32(const float *rx_words, int64_t rx_ld, const int32_t *bits, int64_t bits_ld, int64_t n_words,
+                            const int32_t *support_idx, const int32_t *query_idx, int32_t n_steps, float *W_ih0, float *W_hh0,
+                            float *b_ih0, float *b_hh0, float *W_ih1, float *W_hh1, float *b_ih1, float *b_hh1, float *fc_W,
+                            float *fc_b, float *exp_avg, float *exp_avg_sq, int64_t step0, float meta_lr, float lr, float beta1,
+                            float beta2, float eps, float *loss_out, void *workspace, size_t workspace_bytes, int32_t *status,
+                            int32_t T, mvn_stream_t stream) {
+    if (T < 1 || T > kLstmTrainMaxT || rx_ld < T || bits_ld < T || n_steps < 0 || n_words < 1 || step0 < 0) return MVN_E_DIMS;
+    if (n_steps == 0) return MVN_OK;
+    LstmMetaArgs a = {};
+    float *w[10] = {W_ih0, W_hh0, b_ih0, b_hh0, W_ih1, W_hh1, b_ih1, b_hh1, fc_W, fc_b};
+    for (int i = 0; i < 10; ++i) {
+        if (!w[i]) return MVN_E_NULL;
+        a.w[i] = w[i];
+    }
+    if (!rx_words || !bits || !support_idx || !query_idx || !exp_avg || !exp_avg_sq || !workspace) return MVN_E_NULL;
+    if (workspace_bytes < lt_maml_ws_floats(T) * sizeof(float) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
+    a.y = rx_words;
+    a.y_ld = rx_ld;
+    a.bits = bits;
+    a.bits_ld = bits_ld;
+    a.support_of_step = support_idx;
+    a.word_of_iter = query_idx;
+    a.n_iter = n_steps;
+    a.m = exp_avg;
+    a.v = exp_avg_sq;
+    a.step0 = step0;
+    a.meta_lr = meta_lr;
+    a.lr = lr;
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.eps = eps;
+    a.loss_out = loss_out;
+    a.ws = (float *)workspace;
+    a.ws_bytes = (unsigned)(lt_ws_floats(T) * sizeof(float));  // (the fast-weight image behind it has a resource of its own)
+    a.status = status;
+    a.T = T;
+    return launch_lstm_maml(a, (hipStream_t)stream);
+}
+
+int mvn_lstm_maml_kernel_name(int32_t T, char *name, int32_t name_len) {
+    if (T < 1 || T > kLstmTrainMaxT) return MVN_E_DIMS;
+    if (!name || name_len < 1) return MVN_E_NULL;
+    snprintf(name, (size_t)name_len, "lstm_maml_kernel x %d (first order, support + query pass per step)", kLtGroups);
+    return MVN_OK;
+}
+
 }  // extern "C"

@@ -239,17 +239,27 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     observer: called at the end of every block of the update branches with a dict {stage: 'end', count, ser, pushed,
     buffer_rx, buffer_tx, meta: (support_idx [n, W], query_idx [n]) or None, trained, batch_idx, detector, saved_detector},
     and with stage 'meta' right after a meta-learning update launched by the HIP kernel: what a test needs to replay the
-    block's updates on another implementation (tests/test_gpu_replay.py)."""
+    block's updates on another implementation (tests/test_gpu_replay.py).
+    An LSTMDetector with online_trainer=LSTMMetaTrainer(detector) runs the same branches as the Meta-LSTM curve
+    (meta_lstm_trainer.py): meta_detector defaults to MetaLSTMDetector(), every meta update is ONE maml_training call (first order
+    with window_size 1: one launch of mvn_lstm_maml_train_f32; otherwise the trainer's autograd route), graphed_meta does not apply,
+    weights_init='random' re-initialises the detector in place like LSTMDetector() and resets the optimizer, and
+    meta_style_online_training=True is MetaLSTMTrainer.online_training."""
     import copy
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
 
-    from .lstm import LSTMDetector, LSTMOnlineTrainer, MetaLSTMDetector
+    from .lstm import LSTMDetector, LSTMMetaTrainer, LSTMOnlineTrainer, MetaLSTMDetector
 
+    lstm_meta = False  # the Meta-LSTM curve: an LSTMDetector meta-learned by an LSTMMetaTrainer (meta_lstm_trainer.py)
     if isinstance(detector, (LSTMDetector, MetaLSTMDetector)):
         if online_meta:
-            raise ValueError("eval_by_word: meta-learning of the LSTM detector is not built (meta_lstm_trainer.py); run it without "
-                             "online_meta")
+            if not (isinstance(detector, LSTMDetector) and isinstance(online_trainer, LSTMMetaTrainer)):
+                raise ValueError("eval_by_word: meta-learning of an LSTMDetector needs online_trainer=LSTMMetaTrainer(detector) "
+                                 "(meta_lstm_trainer.py)")
+            lstm_meta = True
+            if meta_detector is None:
+                meta_detector = MetaLSTMDetector()
         if (self_supervised or online_trainer is not None) and not (isinstance(detector, LSTMDetector)
                                                                     and isinstance(online_trainer, LSTMOnlineTrainer)):
             raise ValueError("eval_by_word: online training of an LSTMDetector needs online_trainer=LSTMOnlineTrainer(detector) "
@@ -291,7 +301,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     if weights_init not in ("last_frame", "random", "meta_training"):
         raise ValueError("No such weights init!!!")
     if weights_init == "meta_training" and meta_training_weights is None:
-        raise ValueError("weights_init='meta_training' needs meta_training_weights (six arrays in parameters() order)")
+        raise ValueError("weights_init='meta_training' needs meta_training_weights (the arrays in parameters() order)")
     if online_meta and meta_detector is None:
         raise ValueError("online_meta needs a META_VNETDetector")
     saved_detector = copy.deepcopy(detector) if (online_meta or meta_style_online_training) else None  # :275
@@ -304,8 +314,13 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     meta_step = None  # meta.GraphedMetaStep, built at the first meta update (graphed_meta and a CUDA detector)
     graphed_meta = graphed_meta and rx.is_cuda and (online_trainer is None or online_trainer.optimizer_type == "Adam")  # captured Adam update
     # mvn_vnet_maml_train_f32: the LDS holds 4 parameter vectors (n_states <= 32); the kernel's optimizer is Adam
-    hip_meta = (hip_meta and online_meta and rx.is_cuda and detector.n_states <= 32 and online_trainer is not None
-                and online_trainer.optimizer_type == "Adam" and online_trainer.use_kernel)
+    if lstm_meta:
+        # every step of an update in ONE LSTMMetaTrainer.maml_training call, which takes the kernel (first order, one support word:
+        # one launch) or autograd by its own meta_kernel_route; nothing is captured into a graph
+        graphed_meta, hip_meta = False, True
+    else:
+        hip_meta = (hip_meta and online_meta and rx.is_cuda and detector.n_states <= 32 and online_trainer is not None
+                    and online_trainer.optimizer_type == "Adam" and online_trainer.use_kernel)
     support_idx = torch.arange(-window_size - 1, -1, device=rx.device).long()  # :288
     query_idx = -1 * torch.ones(1, device=rx.device).long()
 
@@ -375,7 +390,10 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
             if weights_init == "last_frame":  # meta_weights_init (:356-366)
                 copy_model(source_model=saved_detector, dest_model=detector)
             elif weights_init == "random":
-                if draws is not None:  # this trial's own stream (what lets trials.eval_by_word_batched replay the run)
+                if lstm_meta:  # initialize_detector (meta_lstm_trainer.py:26-30): what LSTMDetector() draws, in place
+                    detector.lstm.reset_parameters()
+                    detector.fc.reset_parameters()
+                elif draws is not None:  # this trial's own stream (what lets trials.eval_by_word_batched replay the run)
                     with torch.no_grad():
                         for p_, w_ in zip(detector.parameters(), draws.init_weights(detector.n_states)):
                             p_.copy_(w_)

@@ -3,8 +3,9 @@ python_code/detectors/LSTM/lstm_detector.py and detectors/META_LSTM/meta_lstm_de
 libmvn_hip.so (mvn_lstm_decode_f32: window, both layers, fc and argmax in one kernel); every other phase returns the logits from
 torch autograd.  LSTMOnlineTrainer trains an LSTMDetector -- online on one word (lstm_trainer.py:42-53, meta_lstm_trainer.py:48-60)
 or jointly, one word per step (trainer.py:470-479) -- with every iteration of a call inside one launch of mvn_lstm_train_f32
-(forward, CrossEntropy, backward through time and the optimizer step; csrc/lstm_train.inc).  LSTM meta-learning (MAML through the
-unrolled cell) is not built: harness.eval_by_word refuses online_meta with these detectors."""
+(forward, CrossEntropy, backward through time and the optimizer step; csrc/lstm_train.inc).  LSTMMetaTrainer adds the online
+meta-learning of MetaLSTMTrainer (Trainer.meta_train_loop, trainer.py:425-453): first order with one support word per step in one
+launch of mvn_lstm_maml_train_f32, second order and longer windows through MetaLSTMDetector on torch autograd."""
 import torch
 import torch.nn as nn
 from torch.nn import functional as F
@@ -151,7 +152,7 @@ class LSTMOnlineTrainer(OnlineTrainer):
         self._unchecked = False
 
     def maml_training(self, *args, **kwargs):
-        raise NotImplementedError("LSTM meta-learning is not built")
+        raise NotImplementedError("LSTMOnlineTrainer does not meta-learn: use LSTMMetaTrainer(detector)")
 
     def kernel_route(self, T: int) -> bool:
         """Does a call on words of length T run mvn_lstm_train_f32?"""
@@ -236,4 +237,81 @@ class LSTMOnlineTrainer(OnlineTrainer):
             self.optimizer_step(torch.autograd.grad(loss, p))
             if return_loss:
                 losses.append(loss.detach())
+        return torch.stack(losses).to(torch.float32) if return_loss else None
+
+
+class LSTMMetaTrainer(LSTMOnlineTrainer):
+    """LSTMOnlineTrainer plus the online meta-learning of the Meta-LSTM curve: Trainer.meta_train_loop (trainer.py:425-453) as
+    MetaLSTMTrainer runs it from eval_by_word (:331-343), on the same optimizer state as online_training.  First-order steps
+    (MAML=False) with one support word run on the GPU, every step of a call inside one launch of mvn_lstm_maml_train_f32
+    (csrc/lstm_train.inc); second order, several support words, a CPU detector, a word longer than TRAIN_MAX_T and
+    use_kernel=False take torch autograd through MetaLSTMDetector on the same state (meta_kernel_route says which)."""
+
+    # use_kernel=True stays the default for the first-order route: 2.18 ms against 220 ms per step at T = 136
+    # (profiles/lstm_meta_time.txt, DESIGN.md 5.11)
+    def meta_kernel_route(self, T: int, W: int = 1, MAML: bool = False) -> bool:
+        """Does a maml_training call on words of length T with W support words per step run mvn_lstm_maml_train_f32?"""
+        return bool(self.kernel_route(T) and W == 1 and not MAML)
+
+    def maml_training(self, rx_words: torch.Tensor, tx_words: torch.Tensor, support_idx: torch.Tensor, query_idx: torch.Tensor,
+                      meta_lr: float, MAML: bool = True, return_loss: bool = False, labels: torch.Tensor = None):
+        """n meta-learning steps, OnlineTrainer.maml_training's semantics: rx_words / tx_words [Nw, T] the buffered received words
+        and their bits (the labels); support_idx [n, W], query_idx [n] the words of every step (negative indices count from the
+        end).  Uses and advances the same optimizer state as online_training.  Returns the query losses [n] if return_loss.
+        labels is accepted for OnlineTrainer's signature and unused (the labels are tx_words)."""
+        p = self.params
+        dev = p[0].device
+        Nw, T = rx_words.shape
+        qry = torch.remainder(query_idx.to(dev).reshape(-1).long(), Nw)
+        n = qry.numel()
+        sup = torch.remainder(support_idx.to(dev).reshape(n, -1).long(), Nw)
+        W = sup.shape[1]
+        if not self.meta_kernel_route(T, W, MAML):
+            return self._maml_autograd(rx_words, tx_words, sup, qry, meta_lr, MAML, return_loss)
+        _lib.require_gpu_tensor(rx_words, "rx_words")
+        y = _lib.f32c(rx_words)
+        bits = tx_words.detach().to(device=dev, dtype=torch.int32).contiguous()
+        sup32, qry32 = sup.reshape(-1).to(torch.int32).contiguous(), qry.to(torch.int32).contiguous()
+        for t in p:
+            if not t.data.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("LSTM parameters must be contiguous fp32")
+        loss = torch.empty(n, dtype=torch.float32, device=dev) if return_loss else None
+        ws = self._meta_workspace(T, dev)
+        b1, b2, eps = self.kernel_optimizer_args()
+        with _lib.on_device(dev):
+            rc = _lib.load().mvn_lstm_maml_train_f32(_lib.ptr(y), T, _lib.ptr(bits), T, Nw, _lib.ptr(sup32), _lib.ptr(qry32), n,
+                                                     *[_lib.ptr(t.data) for t in p], _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                                                     self.step, meta_lr, self.lr, b1, b2, eps, _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
+                                                     _lib.ptr(self.status), T, _lib.current_stream(dev))
+        _lib.check(rc, "mvn_lstm_maml_train_f32")
+        self._unchecked = True
+        self.step += n
+        return loss
+
+    def _meta_workspace(self, T: int, dev) -> torch.Tensor:
+        """The training workspace with the fast-weight image behind it (3.7 MB at T = 256); online_training shares it."""
+        ws = getattr(self, "_ws", None)
+        need = int(_lib.load().mvn_lstm_maml_workspace_bytes(T))
+        if ws is None or ws.device != dev or ws.numel() < need:
+            ws = self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    def _maml_autograd(self, rx, tx, sup, qry, meta_lr, MAML, return_loss):
+        """meta.meta_train_loop with MetaLSTMTrainer's loss (meta_lstm_trainer.py:38-46: CrossEntropy over reshape(-1, 2) against
+        the bits), step after step on stock autograd; 'train' of MetaLSTMDetector differentiates twice."""
+        p = self.params
+        dev = p[0].device
+        y = rx.detach().to(device=dev, dtype=p[0].dtype)
+        lab = tx.detach().to(dev).long()
+        meta_detector = MetaLSTMDetector()
+        losses = []
+        for k in range(qry.numel()):
+            s, q = sup[k], qry[k:k + 1]
+            loss_supp = F.cross_entropy(meta_detector(y[s], "train", p).reshape(-1, N_CLASSES), lab[s].reshape(-1))
+            local_grad = torch.autograd.grad(loss_supp, p, create_graph=MAML)
+            updated = [w - meta_lr * g for g, w in zip(local_grad, p)]
+            loss_query = F.cross_entropy(meta_detector(y[q], "train", updated).reshape(-1, N_CLASSES), lab[q].reshape(-1))
+            self.optimizer_step(torch.autograd.grad(loss_query, p, create_graph=False))
+            if return_loss:
+                losses.append(loss_query.detach())
         return torch.stack(losses).to(torch.float32) if return_loss else None
