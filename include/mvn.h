@@ -519,6 +519,57 @@ int mvn_lstm_maml_train_f32(const float *rx_words, int64_t rx_ld, const int32_t 
                             int32_t T, mvn_stream_t stream);
 int mvn_lstm_maml_kernel_name(int32_t T, char *name, int32_t name_len);
 
+/* The LSTM trial axis: R independent trials of mvn_lstm_train_f32 / mvn_lstm_maml_train_f32 in one call (lstm_train.inc:
+ * lstm_train_trials_kernel, lstm_maml_trials_kernel), and R detections side by side (lstm.inc, the trial as the second grid
+ * dimension).  A training launch serves P = mvn_lstm_trials_per_launch() = min(8, CUs / 64) trials with 64 workgroups each -- 4 on
+ * an MI355X -- so the whole grid is resident, one workgroup per CU; the call takes the trials with n_iter > 0 in trial order, P at a
+ * time on the stream, and continues a trial of more than 8192 iterations (4096 meta-learning steps) in further launches.
+ * MVN_LSTM_TRIALS_PER_LAUNCH=1..8 pins P below the device's value (tests, A/B runs).  Every trial runs the code of the single-trial
+ * call on its own state, so its parameters, moments and losses are bit for bit those of that call on the trial alone; trials finish
+ * independently, and a trial whose device-wide wait is abandoned writes NaN over ITS parameters and sets ITS status word.
+ *   trials: HOST array of R descriptors, read before the call returns.  y / bits: the trial's words [n_words, T] with the call's
+ *   row strides.  Training: iteration i trains on word word_of_iter[i] (NULL: word 0) and, for M > 0, on the positions
+ *   idx[i * M .. i * M + M).  Meta-learning: step k has support word idx[k] and query word word_of_iter[k].  params: the ten tensors
+ *   flat in parameters() order (795138 floats), 16-byte aligned; exp_avg / exp_avg_sq [795138]; loss_out [n_iter] or NULL;
+ *   workspace: mvn_lstm_train_workspace_bytes(T) resp. mvn_lstm_maml_workspace_bytes(T) bytes, 16-byte aligned; status: device
+ *   int32 or NULL.  Two trials of one call must NOT share params, moments, workspace, loss_out or status (not checked: the call
+ *   cannot see device memory).  A trial with n_iter == 0 is not launched and nothing of it is read or written.
+ * Checked before any device call, shapes before pointers: MVN_E_DIMS for R < 0, T outside [1, MVN_LSTM_TRAIN_MAX_T], a row stride
+ * < T, M < 0, M > T, or any trial with n_iter < 0, n_words < 1 or step0 < 0; MVN_OK for R == 0 or no trial with n_iter > 0;
+ * MVN_E_NULL for a missing pointer of a trial with n_iter > 0 (loss_out and status may be NULL); MVN_E_WORKSPACE for a missing or
+ * misaligned workspace (or misaligned params); MVN_E_DEVICE on a device with fewer than 64 CUs.
+ * mvn_lstm_decode_trials_f32: y [R B, y_ld >= T], trial r's words in rows r B .. r B + B - 1; dec [R B, dec_ld >= T] and logits
+ * [R B, T, 2] (or NULL) likewise; params: the stacked bank, trial r's ten tensors flat at params + r param_ld, param_ld >= 795138
+ * and a multiple of 4 (795138 is 2 mod 4 and the training kernels read the matrices with 16-byte loads: a bank stacked at the
+ * natural stride would misalign every odd trial); workspace: mvn_lstm_decode_trials_workspace_bytes(R, B, T) bytes, 16-byte aligned.
+ * A trial's decisions and logits are bit for bit those of mvn_lstm_decode_f32 on that trial alone.
+ * mvn_lstm_train_trials_kernel_name: the launches of a training (meta = 0) or meta-learning (meta = 1) trials call. */
+typedef struct mvn_lstm_trial {
+    const float *y;
+    const int32_t *bits;
+    int64_t n_words;
+    const int32_t *word_of_iter;
+    const int32_t *idx;
+    float *params;
+    float *exp_avg, *exp_avg_sq;
+    float *loss_out;
+    void *workspace;
+    int32_t *status;
+    int64_t step0;
+    int32_t n_iter;
+    int32_t reserved;
+} mvn_lstm_trial_t;
+int32_t mvn_lstm_trials_per_launch(void);
+int mvn_lstm_train_trials_f32(const mvn_lstm_trial_t *trials, int32_t R, int64_t y_ld, int64_t bits_ld, int32_t M, float lr, float beta1,
+                              float beta2, float eps, int32_t T, mvn_stream_t stream);
+int mvn_lstm_maml_train_trials_f32(const mvn_lstm_trial_t *trials, int32_t R, int64_t rx_ld, int64_t bits_ld, float meta_lr, float lr,
+                                   float beta1, float beta2, float eps, int32_t T, mvn_stream_t stream);
+int mvn_lstm_train_trials_kernel_name(int32_t R, int32_t T, int32_t meta, char *name, int32_t name_len);
+size_t mvn_lstm_decode_trials_workspace_bytes(int32_t R, int64_t B, int32_t T);
+int mvn_lstm_decode_trials_f32(const float *y, int64_t y_ld, const float *params, int64_t param_ld, float *dec, int64_t dec_ld,
+                               float *logits, void *workspace, size_t workspace_bytes, int32_t R, int64_t B, int32_t T,
+                               mvn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,7 +78,21 @@ SIGNATURES = {
     "mvn_lstm_maml_train_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i32] + [_vp] * 12 +
                                 [_i64] + [ctypes.c_float] * 5 + [_vp, _vp, ctypes.c_size_t, _vp, _i32, _vp]),
     "mvn_lstm_maml_kernel_name": (ctypes.c_int, [_i32, ctypes.c_char_p, _i32]),
+    "mvn_lstm_trials_per_launch": (_i32, []),
+    "mvn_lstm_train_trials_f32": (ctypes.c_int, [_vp, _i32, _i64, _i64, _i32] + [ctypes.c_float] * 4 + [_i32, _vp]),
+    "mvn_lstm_maml_train_trials_f32": (ctypes.c_int, [_vp, _i32, _i64, _i64] + [ctypes.c_float] * 5 + [_i32, _vp]),
+    "mvn_lstm_train_trials_kernel_name": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_char_p, _i32]),
+    "mvn_lstm_decode_trials_workspace_bytes": (ctypes.c_size_t, [_i32, _i64, _i32]),
+    "mvn_lstm_decode_trials_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, ctypes.c_size_t, _i32, _i64, _i32, _vp]),
 }
+
+
+class LstmTrial(ctypes.Structure):
+    """include/mvn.h: mvn_lstm_trial_t, one trial of mvn_lstm_train_trials_f32 / mvn_lstm_maml_train_trials_f32 (a HOST array of
+    these is read by the call before it returns)."""
+    _fields_ = [("y", _vp), ("bits", _vp), ("n_words", _i64), ("word_of_iter", _vp), ("idx", _vp), ("params", _vp), ("exp_avg", _vp),
+                ("exp_avg_sq", _vp), ("loss_out", _vp), ("workspace", _vp), ("status", _vp), ("step0", _i64), ("n_iter", _i32),
+                ("reserved", _i32)]
 
 _lib = None
 

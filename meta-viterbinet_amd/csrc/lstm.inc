@@ -20,6 +20,8 @@
 // order (one global_load_dwordx4 per lane covers 4 k-steps of one gate tile), and every step streams them from L2; the four waves
 // of a SIMD cover each other's load latency (a register prefetch of the next k-group spills at the 128-VGPR cap).
 // fc and the decision of step t run on the first 2 * BW lanes during step t + 1's first layer (after the loop for t = T - 1).
+// Both kernels take a TRIAL as the second grid dimension (mvn_lstm_decode_trials_f32): R weight sets packed side by side, workgroup
+// (x, r) decoding words 16 x .. 16 x + 15 of trial r with trial r's weights.
 constexpr int kLstmIn = 4, kLstmH = 256, kLstmGates = 4 * kLstmH, kLstmWaves = 16;
 constexpr float kLstmPad = -100.0f;  // START_VALUE_PADDING, lstm_detector.py:10
 // packed workspace, in floats: W_ih0 [wave][gate][lane]; W_hh0, W_ih1, W_hh1 [wave][k-group of 16][gate][lane][4];
@@ -41,25 +43,27 @@ __device__ __forceinline__ float lstm_tanh(float x) {
     return copysignf((1.0f - e) / (1.0f + e), x);
 }
 
-// one thread per packed float
-__global__ __launch_bounds__(256) void lstm_pack_kernel(const LstmWeights wt, float *__restrict__ pk) {
+// one thread per packed float; blockIdx.y = trial: its ten tensors lie param_ld floats behind the previous trial's, its packed
+// image kLstmPkFloats behind the previous one
+__global__ __launch_bounds__(256) void lstm_pack_kernel(const LstmWeights wt, int64_t param_ld, float *__restrict__ pk) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= kLstmPkFloats) return;
+    const int64_t po = (int64_t)blockIdx.y * param_ld;  // this trial's offset into every tensor
     float v;
     if (e < kLstmPkHh0) {  // [wave][gate][lane] = W_ih0[256 gate + 16 wave + (lane & 15)][lane >> 4]
         const int lane = (int)(e & 63), g = (int)(e >> 6) & 3, w = (int)(e >> 8);
-        v = wt.w[0][(256 * g + 16 * w + (lane & 15)) * kLstmIn + (lane >> 4)];
+        v = wt.w[0][po + (256 * g + 16 * w + (lane & 15)) * kLstmIn + (lane >> 4)];
     } else if (e < kLstmPkBias) {  // [wave][kg][gate][lane][s] = W[256 gate + 16 wave + (lane & 15)][16 kg + 4 s + (lane >> 4)]
         const int m = (int)((e - kLstmPkHh0) / kLstmPkMat);
         const size_t r = (e - kLstmPkHh0) % kLstmPkMat;
         const int s = (int)(r & 3), lane = (int)(r >> 2) & 63, g = (int)(r >> 8) & 3, kg = (int)(r >> 10) & 15, w = (int)(r >> 14);
         const float *src = wt.w[m == 0 ? 1 : (m == 1 ? 4 : 5)];
-        v = src[(256 * g + 16 * w + (lane & 15)) * kLstmH + 16 * kg + 4 * s + (lane >> 4)];
+        v = src[po + (256 * g + 16 * w + (lane & 15)) * kLstmH + 16 * kg + 4 * s + (lane >> 4)];
     } else {
         const int l = (int)((e - kLstmPkBias) / kLstmGates), n = (int)((e - kLstmPkBias) % kLstmGates);
-        v = wt.w[4 * l + 2][n] + wt.w[4 * l + 3][n];
+        v = wt.w[4 * l + 2][po + n] + wt.w[4 * l + 3][po + n];
     }
-    pk[e] = v;
+    pk[(size_t)blockIdx.y * kLstmPkFloats + e] = v;
 }
 
 // LDS float index of h[word m][unit k] in a buffer of BW words: [k-group][k & 3][m][(k >> 2) & 3]
@@ -135,11 +139,14 @@ __device__ __forceinline__ void lstm_fc(const float *hb, const float *fcw, float
     }
 }
 
-template <int MT>
+// TRIALS: blockIdx.y = trial (mvn_lstm_decode_trials_f32); false keeps the single-trial launch the code it was, instruction for
+// instruction (the trial offsets cost the register allocation 8 VGPRs and 2.5 % of the kernel's time at 1 x 136)
+template <int MT, bool TRIALS = false>
 __global__ __launch_bounds__(64 * kLstmWaves) void lstm_decode_kernel(const float *__restrict__ y, int64_t y_ld,
                                                                       const float *__restrict__ pk, const float *__restrict__ fc_w,
                                                                       const float *__restrict__ fc_b, float *__restrict__ dec,
-                                                                      int64_t dec_ld, float *__restrict__ logits, int64_t B, int T) {
+                                                                      int64_t dec_ld, float *__restrict__ logits, int64_t B, int T,
+                                                                      int64_t param_ld) {
     constexpr int BW = 16 * MT;
     constexpr int HBUF = BW * kLstmH;  // floats of one h buffer
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -148,28 +155,32 @@ __global__ __launch_bounds__(64 * kLstmWaves) void lstm_decode_kernel(const floa
     float *fcw = smem + 4 * HBUF;  // [2][256]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, q = lane >> 4;
-    const int64_t b0 = (int64_t)blockIdx.x * BW;
+    // blockIdx.y = trial r: rows r B .. r B + B - 1 of y / dec / logits (B_end = their end), its own packed weights and fc layer
+    const int64_t trial = TRIALS ? blockIdx.y : 0;
+    const int64_t row0 = trial * B, B_end = row0 + B, b0 = row0 + (int64_t)blockIdx.x * BW;
+    const float *__restrict__ pkr = pk + trial * (int64_t)kLstmPkFloats;
+    const int64_t po = trial * param_ld;
 
     for (int i = tid; i < HBUF; i += 64 * kLstmWaves) {  // h(-1) = 0 (buffer 1 of both layers)
         h0[HBUF + i] = 0.0f;
         h1[HBUF + i] = 0.0f;
     }
-    for (int i = tid; i < 2 * kLstmH; i += 64 * kLstmWaves) fcw[i] = fc_w[i];
-    const float fcb = tid < 2 * BW ? fc_b[tid & 1] : 0.0f;
+    for (int i = tid; i < 2 * kLstmH; i += 64 * kLstmWaves) fcw[i] = fc_w[po + i];
+    const float fcb = tid < 2 * BW ? fc_b[po + (tid & 1)] : 0.0f;
 
     const int u = 16 * wave + j;  // this lane's hidden unit (C column)
     float bias0[4], bias1[4], wih0[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        bias0[g] = pk[kLstmPkBias + 256 * g + u];
-        bias1[g] = pk[kLstmPkBias + kLstmGates + 256 * g + u];
-        wih0[g] = pk[kLstmPkIh0 + (wave * 4 + g) * 64 + lane];
+        bias0[g] = pkr[kLstmPkBias + 256 * g + u];
+        bias1[g] = pkr[kLstmPkBias + kLstmGates + 256 * g + u];
+        wih0[g] = pkr[kLstmPkIh0 + (wave * 4 + g) * 64 + lane];
     }
-    const float *yrow[MT];  // A fragment of x_t: word 16 mt + j, input k = q (rows past B read row B - 1; nothing is stored for them)
+    const float *yrow[MT];  // A fragment of x_t: word 16 mt + j, input k = q (rows past the trial's last read that one; nothing is stored for them)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int64_t b = b0 + 16 * mt + j;
-        yrow[mt] = y + (b < B ? b : B - 1) * y_ld;
+        yrow[mt] = y + (b < B_end ? b : B_end - 1) * y_ld;
     }
     float xn[MT];
 #pragma unroll
@@ -180,7 +191,7 @@ __global__ __launch_bounds__(64 * kLstmWaves) void lstm_decode_kernel(const floa
 #pragma unroll
         for (int r = 0; r < 4; ++r) c0[mt][r] = c1[mt][r] = 0.0f;
 
-    const f32x4 *pk4 = reinterpret_cast<const f32x4 *>(pk);
+    const f32x4 *pk4 = reinterpret_cast<const f32x4 *>(pkr);
     const f32x4 *whh0 = pk4 + (kLstmPkHh0 + (size_t)wave * 16384) / 4;
     const f32x4 *wih1 = pk4 + (kLstmPkIh1 + (size_t)wave * 16384) / 4;
     const f32x4 *whh1 = pk4 + (kLstmPkHh1 + (size_t)wave * 16384) / 4;
@@ -206,7 +217,7 @@ __global__ __launch_bounds__(64 * kLstmWaves) void lstm_decode_kernel(const floa
             }
         lstm_matvec<MT>(acc, whh0, reinterpret_cast<const f32x4 *>(h0 + prv * HBUF), lane);
         lstm_cell<MT>(acc, c0, h0 + cur * HBUF, wave, lane);
-        if (t > 0 && tid < 2 * BW) lstm_fc<BW>(h1 + prv * HBUF, fcw, fcb, tid, b0, B, T, t - 1, dec, dec_ld, logits);
+        if (t > 0 && tid < 2 * BW) lstm_fc<BW>(h1 + prv * HBUF, fcw, fcb, tid, b0, B_end, T, t - 1, dec, dec_ld, logits);
         __syncthreads();
         // layer 1
 #pragma unroll
@@ -218,20 +229,22 @@ __global__ __launch_bounds__(64 * kLstmWaves) void lstm_decode_kernel(const floa
         lstm_cell<MT>(acc, c1, h1 + cur * HBUF, wave, lane);
         __syncthreads();
     }
-    if (tid < 2 * BW) lstm_fc<BW>(h1 + ((T - 1) & 1) * HBUF, fcw, fcb, tid, b0, B, T, T - 1, dec, dec_ld, logits);
+    if (tid < 2 * BW) lstm_fc<BW>(h1 + ((T - 1) & 1) * HBUF, fcw, fcb, tid, b0, B_end, T, T - 1, dec, dec_ld, logits);
 }
 
 constexpr size_t lstm_lds_bytes(int mt) { return ((size_t)4 * 16 * mt * kLstmH + 2 * kLstmH) * sizeof(float); }
 
 // One form: MT = 1 (16 words per workgroup, 98 VGPRs, no scratch).  MT = 2 (each B fragment serving two M-tiles, half the L2
 // traffic) needs 14 VGPRs more than the 128 a 1024-thread workgroup may hold and spills; it is not launched (DESIGN 5.9).
+// R trials (grid y): trial r's tensors at wt.w[i] + r param_ld, its B words at row r B of y / dec / logits
 int launch_lstm_decode(const float *y, int64_t y_ld, const LstmWeights &wt, float *dec, int64_t dec_ld, float *logits, float *pk,
-                       int64_t B, int T, hipStream_t st) {
-    hipLaunchKernelGGL(lstm_pack_kernel, dim3((unsigned)((kLstmPkFloats + 255) / 256)), dim3(256), 0, st, wt, pk);
-    const dim3 grid((unsigned)((B + 15) / 16));
+                       int64_t B, int T, hipStream_t st, int R = 1, int64_t param_ld = 0) {
+    hipLaunchKernelGGL(lstm_pack_kernel, dim3((unsigned)((kLstmPkFloats + 255) / 256), (unsigned)R), dim3(256), 0, st, wt, param_ld, pk);
+    const dim3 grid((unsigned)((B + 15) / 16), (unsigned)R);
     const size_t lds = lstm_lds_bytes(1);
-    if (int e = ensure_dynamic_lds((const void *)lstm_decode_kernel<1>, lds)) return e;
-    hipLaunchKernelGGL(lstm_decode_kernel<1>, grid, dim3(64 * kLstmWaves), lds, st, y, y_ld, (const float *)pk, wt.w[8], wt.w[9], dec,
-                       dec_ld, logits, B, T);
+    const auto kernel = R > 1 ? lstm_decode_kernel<1, true> : lstm_decode_kernel<1, false>;
+    if (int e = ensure_dynamic_lds((const void *)kernel, lds)) return e;
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * kLstmWaves), lds, st, y, y_ld, (const float *)pk, wt.w[8], wt.w[9], dec,
+                       dec_ld, logits, B, T, param_ld);
     return (int)hipGetLastError();
 }

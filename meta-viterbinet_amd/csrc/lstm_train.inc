@@ -25,6 +25,8 @@
 // parameters it owns and sets *status = 1.
 // lstm_maml_kernel is the same body run twice per step (support pass, query pass): first-order online meta-learning, see
 // LstmMetaArgs below.
+// lstm_train_trials_kernel / lstm_maml_trials_kernel run the same body for up to 8 independent trials in one launch, 64 workgroups
+// and one workspace region each (LstmTrialsArgs below).
 constexpr int kLtGroups = 64, kLtThreads = 256, kLtU = kLstmH / kLtGroups, kLtR = 4 * kLtU;
 constexpr int kLstmTrainMaxT = 256;       // LDS: 40 T floats of saved activations beside 96 KB of weights
 constexpr int kLstmTrainMaxIter = 8192;   // iterations per launch (the arrival counter is 32 bits wide)
@@ -119,7 +121,7 @@ constexpr size_t kLtFastFcb = kLtFastFc + 2 * kLstmH, kLtFastFloats = kLtFastFcb
 __host__ __device__ constexpr size_t lt_maml_ws_floats(int T) { return lt_ws_floats(T) + kLtFastFloats; }
 
 template <bool META, class Args>
-__device__ __forceinline__ void lstm_train_body(const Args a) {  // (by value: a reference costs lstm_train_kernel three VGPRs)
+__device__ __forceinline__ void lstm_train_body(const Args a, const int g) {  // (by value: a reference costs lstm_train_kernel three VGPRs)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int T = a.T, Tp = (T + 3) & ~3, M = a.M;
     const LtLds L(T);
@@ -127,7 +129,7 @@ __device__ __forceinline__ void lstm_train_body(const Args a) {  // (by value: a
     float *hbuf = smem + L.hbuf, *dgbuf = smem + L.dgbuf, *part = smem + L.part, *yw = smem + L.yw, *dl = smem + L.dl;
     float *nll = smem + L.nll, *cnt = smem + L.cnt, *saved = smem + L.saved;
     int *lab = reinterpret_cast<int *>(smem + L.lab), *idxs = reinterpret_cast<int *>(smem + L.idx);
-    const int tid = threadIdx.x, g = blockIdx.x;
+    const int tid = threadIdx.x;  // g: this workgroup's group number within its trial
     GroupSync *gs = reinterpret_cast<GroupSync *>(a.ws);
     const SlotIO io(a.ws, a.ws_bytes);  // same_xcd stays false: write-through stores, sc1 loads
     const SlotIO mhh0(a.w[1], kLstmGates * kLstmH * 4), mih1(a.w[4], kLstmGates * kLstmH * 4), mhh1(a.w[5], kLstmGates * kLstmH * 4);
@@ -445,8 +447,70 @@ __device__ __forceinline__ void lstm_train_body(const Args a) {  // (by value: a
     if (tid == 0 && a.status) *a.status = 1;
 }
 
-__global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainArgs a) { lstm_train_body<false>(a); }
-__global__ __launch_bounds__(kLtThreads) void lstm_maml_kernel(const LstmMetaArgs a) { lstm_train_body<true>(a); }
+__global__ __launch_bounds__(kLtThreads) void lstm_train_kernel(const LstmTrainArgs a) { lstm_train_body<false>(a, blockIdx.x); }
+__global__ __launch_bounds__(kLtThreads) void lstm_maml_kernel(const LstmMetaArgs a) { lstm_train_body<true>(a, blockIdx.x); }
+
+// ---- the trial axis: n <= P independent trials in ONE launch of 64 n workgroups.  Workgroup b serves trial slot b / 64 as group
+// b % 64 and runs the body above on that trial's arguments: its own words, weights, moments, loss vector, status word and
+// workspace region (GroupSync, h history, dgates exchange, fast-weight image), so trials share nothing, finish independently, and
+// a trial whose wait is abandoned marks itself alone.  With the dispatcher's round-robin over the XCDs (observed, not promised)
+// every trial has 8 workgroups on every XCD; nothing depends on it.  The training LDS is above 96 KB for every T, so a CU holds
+// one workgroup, and the launcher keeps 64 n <= CUs: the whole grid is resident, and every spin stays bounded all the same.
+constexpr int kLtMaxTrials = 8;
+struct LstmTrialSlot {
+    const float *y;
+    const int *bits;
+    const int *word_of_iter, *idx;  // meta-learning: the query words, the support words
+    float *params, *m, *v;          // the ten tensors flat in parameters() order (kLtOff), the moments
+    float *loss_out;
+    float *ws;
+    int *status;
+    long long step0;
+    int n_iter, pad;
+};
+struct LstmTrialsArgs {
+    LstmTrialSlot slot[kLtMaxTrials];
+    long long y_ld, bits_ld;
+    int M, T;
+    float lr, beta1, beta2, eps, meta_lr;
+    unsigned spin_limit;
+};
+
+template <bool META>
+__device__ __forceinline__ void lstm_trials_body(const LstmTrialsArgs &t) {
+    const LstmTrialSlot &s = t.slot[blockIdx.x / kLtGroups];
+    std::conditional_t<META, LstmMetaArgs, LstmTrainArgs> a;
+    a.y = s.y;
+    a.y_ld = t.y_ld;
+    a.bits = s.bits;
+    a.bits_ld = t.bits_ld;
+    a.word_of_iter = s.word_of_iter;
+    a.idx = META ? nullptr : s.idx;
+    a.M = META ? 0 : t.M;
+    a.n_iter = s.n_iter;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) a.w[i] = s.params + kLtOff[i];
+    a.m = s.m;
+    a.v = s.v;
+    a.step0 = s.step0;
+    a.lr = t.lr;
+    a.beta1 = t.beta1;
+    a.beta2 = t.beta2;
+    a.eps = t.eps;
+    a.loss_out = s.loss_out;
+    a.ws = s.ws;
+    a.ws_bytes = (unsigned)(lt_ws_floats(t.T) * sizeof(float));
+    a.status = s.status;
+    a.T = t.T;
+    a.spin_limit = t.spin_limit;
+    if constexpr (META) {
+        a.support_of_step = s.idx;
+        a.meta_lr = t.meta_lr;
+    }
+    lstm_train_body<META>(a, (int)(blockIdx.x % kLtGroups));
+}
+__global__ __launch_bounds__(kLtThreads) void lstm_train_trials_kernel(const LstmTrialsArgs t) { lstm_trials_body<false>(t); }
+__global__ __launch_bounds__(kLtThreads) void lstm_maml_trials_kernel(const LstmTrialsArgs t) { lstm_trials_body<true>(t); }
 
 // n_iter iterations in launches of at most kLstmTrainMaxIter; the arrival counter is zeroed in front of each
 int launch_lstm_train(LstmTrainArgs a, hipStream_t st) {
@@ -489,6 +553,56 @@ int launch_lstm_maml(LstmMetaArgs a, hipStream_t st) {
         if (a.loss_out) b.loss_out = a.loss_out + done;
         hipLaunchKernelGGL(lstm_maml_kernel, dim3(kLtGroups), dim3(kLtThreads), lds, st, b);
         if (int rc = (int)hipGetLastError()) return rc;
+    }
+    return MVN_OK;
+}
+
+// P, the trials of one launch: min(8, CUs / 64), MVN_LSTM_TRIALS_PER_LAUNCH=1..8 pins it lower (tests, A/B runs); 0 below 64 CUs
+int lstm_trials_per_launch() {
+    const int fit = std::min(kLtMaxTrials, current_device_cus() / kLtGroups);
+    const char e = sw(SW_LSTM_TRIALS_PER_LAUNCH);
+    return e >= '1' && e <= '8' ? std::min(fit, e - '0') : fit;
+}
+
+// The trials of a call with n_iter > 0, in trial order, P at a time on the stream; a trial with more iterations than a launch
+// holds (kLstmTrainMaxIter passes of the loop body) continues in the next launches of its batch, advanced like launch_lstm_train
+// advances it.  The arrival counters of a launch's trials are zeroed in front of it.
+template <bool META>
+int launch_lstm_trials(const LstmTrialSlot *trials, int R, LstmTrialsArgs shared, hipStream_t st) {
+    const int P = lstm_trials_per_launch();
+    if (P < 1) return MVN_E_DEVICE;
+    const auto kernel = META ? lstm_maml_trials_kernel : lstm_train_trials_kernel;
+    const size_t lds = lstm_train_lds_bytes(shared.T);
+    if (int e = ensure_dynamic_lds((const void *)kernel, lstm_train_lds_bytes(kLstmTrainMaxT))) return e;
+    shared.spin_limit = group_spin_limit();
+    const int per = META ? kLstmTrainMaxIter / 2 : kLstmTrainMaxIter;
+    int r = 0;
+    while (r < R) {
+        LstmTrialSlot batch[kLtMaxTrials];
+        int nb = 0;
+        for (; r < R && nb < P; ++r)
+            if (trials[r].n_iter > 0) batch[nb++] = trials[r];
+        for (;;) {
+            int n = 0;
+            for (int b = 0; b < nb; ++b) {
+                LstmTrialSlot &left = batch[b];
+                if (left.n_iter <= 0) continue;
+                LstmTrialSlot &s = shared.slot[n++];
+                s = left;
+                s.n_iter = std::min(per, left.n_iter);
+                hipError_t e = hipMemsetAsync(s.ws, 0, sizeof(GroupSync), st);
+                if (e != hipSuccess) return (int)e;
+                left.n_iter -= s.n_iter;
+                left.step0 += s.n_iter;
+                if (left.word_of_iter) left.word_of_iter += s.n_iter;
+                if (left.idx) left.idx += META ? (long long)s.n_iter : (long long)s.n_iter * shared.M;
+                if (left.loss_out) left.loss_out += s.n_iter;
+            }
+            if (!n) break;
+            for (int b = n; b < kLtMaxTrials; ++b) shared.slot[b] = LstmTrialSlot{};
+            hipLaunchKernelGGL(kernel, dim3(kLtGroups * n), dim3(kLtThreads), lds, st, shared);
+            if (int rc = (int)hipGetLastError()) return rc;
+        }
     }
     return MVN_OK;
 }

@@ -29,6 +29,7 @@
 #include <atomic>
 #include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/mvn.h"
 
@@ -565,10 +566,10 @@ __global__ __launch_bounds__(256) void isi_awgn_kernel(const float *__restrict__
 // They are read from the environment ONCE per process -- the by-word evaluation calls into the library every few
 // microseconds -- and again when the caller asks (mvn_reload_switches: the test-suite flips them between calls).
 enum Switch { SW_UNFUSED, SW_COOP, SW_FUSEDN, SW_GENERIC_SWEEP, SW_VA256, SW_VA_INPLACE, SW_VA16, SW_SWEEP_INPLACE, SW_SWEEP16,
-              SW_TRAIN_GROUPS, SW_TRAIN_PAIR, SW_FUSED_IP, SW_TRAIN_XCD, SW_DEALT, SW_COUNT };
+              SW_TRAIN_GROUPS, SW_TRAIN_PAIR, SW_FUSED_IP, SW_TRAIN_XCD, SW_DEALT, SW_LSTM_TRIALS_PER_LAUNCH, SW_COUNT };
 const char *const kSwitchNames[SW_COUNT] = {"MVN_UNFUSED", "MVN_COOP", "MVN_FUSEDN", "MVN_GENERIC_SWEEP", "MVN_VA256",
                                             "MVN_VA_INPLACE", "MVN_VA16", "MVN_SWEEP_INPLACE", "MVN_SWEEP16", "MVN_TRAIN_GROUPS",
-                                            "MVN_TRAIN_PAIR", "MVN_FUSED_IP", "MVN_TRAIN_XCD", "MVN_DEALT"};
+                                            "MVN_TRAIN_PAIR", "MVN_FUSED_IP", "MVN_TRAIN_XCD", "MVN_DEALT", "MVN_LSTM_TRIALS_PER_LAUNCH"};
 // The library may be called from several host threads: the table is atomics (a reload while another thread launches gives that
 // launch either the old or the new value of a switch, never a torn one), filled under a mutex.
 std::atomic<char> g_switch[SW_COUNT];
@@ -1869,6 +1870,105 @@ int mvn_lstm_maml_kernel_name(int32_t T, char *name, int32_t name_len) {
     if (!name || name_len < 1) return MVN_E_NULL;
     snprintf(name, (size_t)name_len, "lstm_maml_kernel x %d (first order, support + query pass per step)", kLtGroups);
     return MVN_OK;
+}
+
+// ---- the LSTM trial axis: R independent trainings / meta-learnings / detections in one call (lstm_train.inc, lstm.inc) ----
+int32_t mvn_lstm_trials_per_launch(void) { return lstm_trials_per_launch(); }
+
+// shared checks of the two training calls; fills the slots of the trials that run (n_iter > 0)
+static int lstm_trials_validate(const mvn_lstm_trial_t *trials, int32_t R, int64_t y_ld, int64_t bits_ld, int32_t M, int32_t T, bool meta,
+                                std::vector<LstmTrialSlot> &slots) {
+    if (R < 0 || T < 1 || T > kLstmTrainMaxT || y_ld < T || bits_ld < T || M < 0 || M > T) return MVN_E_DIMS;
+    if (R == 0) return MVN_OK;
+    if (!trials) return MVN_E_NULL;
+    for (int r = 0; r < R; ++r)
+        if (trials[r].n_iter < 0 || trials[r].n_words < 1 || trials[r].step0 < 0) return MVN_E_DIMS;
+    for (int r = 0; r < R; ++r) {
+        const mvn_lstm_trial_t &t = trials[r];
+        if (t.n_iter == 0) continue;  // not launched: nothing of it is read or written
+        if (!t.y || !t.bits || !t.params || !t.exp_avg || !t.exp_avg_sq) return MVN_E_NULL;
+        if (meta ? (!t.word_of_iter || !t.idx) : (M > 0 && !t.idx)) return MVN_E_NULL;
+    }
+    for (int r = 0; r < R; ++r) {
+        const mvn_lstm_trial_t &t = trials[r];
+        if (t.n_iter == 0) continue;
+        if (!t.workspace || (reinterpret_cast<uintptr_t>(t.workspace) & 15) || (reinterpret_cast<uintptr_t>(t.params) & 15)) return MVN_E_WORKSPACE;
+        LstmTrialSlot s = {};
+        s.y = t.y;
+        s.bits = t.bits;
+        s.word_of_iter = t.word_of_iter;
+        s.idx = (meta || M > 0) ? t.idx : nullptr;
+        s.params = t.params;
+        s.m = t.exp_avg;
+        s.v = t.exp_avg_sq;
+        s.loss_out = t.loss_out;
+        s.ws = (float *)t.workspace;
+        s.status = t.status;
+        s.step0 = t.step0;
+        s.n_iter = t.n_iter;
+        slots.push_back(s);
+    }
+    return MVN_OK;
+}
+
+int mvn_lstm_train_trials_f32(const mvn_lstm_trial_t *trials, int32_t R, int64_t y_ld, int64_t bits_ld, int32_t M, float lr, float beta1,
+                              float beta2, float eps, int32_t T, mvn_stream_t stream) {
+    std::vector<LstmTrialSlot> slots;
+    if (int rc = lstm_trials_validate(trials, R, y_ld, bits_ld, M, T, false, slots)) return rc;
+    if (slots.empty()) return MVN_OK;
+    LstmTrialsArgs a = {};
+    a.y_ld = y_ld;
+    a.bits_ld = bits_ld;
+    a.M = M;
+    a.T = T;
+    a.lr = lr;
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.eps = eps;
+    return launch_lstm_trials<false>(slots.data(), (int)slots.size(), a, (hipStream_t)stream);
+}
+
+int mvn_lstm_maml_train_trials_f32(const mvn_lstm_trial_t *trials, int32_t R, int64_t rx_ld, int64_t bits_ld, float meta_lr, float lr,
+                                   float beta1, float beta2, float eps, int32_t T, mvn_stream_t stream) {
+    std::vector<LstmTrialSlot> slots;
+    if (int rc = lstm_trials_validate(trials, R, rx_ld, bits_ld, 0, T, true, slots)) return rc;
+    if (slots.empty()) return MVN_OK;
+    LstmTrialsArgs a = {};
+    a.y_ld = rx_ld;
+    a.bits_ld = bits_ld;
+    a.T = T;
+    a.meta_lr = meta_lr;
+    a.lr = lr;
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.eps = eps;
+    return launch_lstm_trials<true>(slots.data(), (int)slots.size(), a, (hipStream_t)stream);
+}
+
+int mvn_lstm_train_trials_kernel_name(int32_t R, int32_t T, int32_t meta, char *name, int32_t name_len) {
+    if (R < 0 || T < 1 || T > kLstmTrainMaxT) return MVN_E_DIMS;
+    if (!name || name_len < 1) return MVN_E_NULL;
+    const int P = lstm_trials_per_launch();
+    snprintf(name, (size_t)name_len, "%s x %d per trial, %d trials per launch", meta ? "lstm_maml_trials_kernel" : "lstm_train_trials_kernel",
+             kLtGroups, P);
+    return MVN_OK;
+}
+
+size_t mvn_lstm_decode_trials_workspace_bytes(int32_t R, int64_t B, int32_t T) {
+    if (R < 1 || B < 1 || T < 1) return 0;
+    return (size_t)R * ((kLstmPkFloats * sizeof(float) + 15) & ~(size_t)15);
+}
+
+int mvn_lstm_decode_trials_f32(const float *y, int64_t y_ld, const float *params, int64_t param_ld, float *dec, int64_t dec_ld,
+                               float *logits, void *workspace, size_t workspace_bytes, int32_t R, int64_t B, int32_t T, mvn_stream_t stream) {
+    if (R < 0 || R > 65535 || B < 0 || T < 1 || y_ld < T || dec_ld < T || param_ld < (int64_t)kLstmParams || (param_ld & 3)) return MVN_E_DIMS;
+    if (R == 0 || B == 0) return MVN_OK;
+    if (!y || !dec || !params) return MVN_E_NULL;
+    if (!workspace || workspace_bytes < mvn_lstm_decode_trials_workspace_bytes(R, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return MVN_E_WORKSPACE;
+    LstmWeights wt;
+    for (int i = 0; i < 10; ++i) wt.w[i] = params + kLtOff[i];
+    return launch_lstm_decode(y, y_ld, wt, dec, dec_ld, logits, (float *)workspace, B, T, (hipStream_t)stream, R, param_ld);
 }
 
 }  // extern "C"

@@ -214,7 +214,19 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     R-word form serve 16 states): trial after trial through harness.eval_by_word, there on the run-time-n_states training kernels.
     cohorts > 1: the trials are split into that many groups that step ALTERNATELY on the same stream: while the GPU works
     through one group's training launches the host takes the decisions and fills the descriptors of the next (the host
-    work of a step can only start after the step's sync).  Same launches per trial, same results."""
+    work of a step can only start after the step's sync).  Same launches per trial, same results.
+    bank may be an lstm_trials.LSTMTrialBank: R LSTM detectors (the LSTM, OnlineRNN and Meta-LSTM curves), same arguments, same
+    return value and `record`, row r equal to harness.eval_by_word run alone on an LSTMDetector with an LSTMMetaTrainer and
+    draws[r].  The lock-step engine of lstm_trials.py then serves self_supervised in both styles, online_meta with MAML=False
+    and window_size=1, weights_init 'last_frame' / 'meta_training', initial_buffer and the three optimizers: per block step one
+    mvn_lstm_decode_trials_f32 launch, the Reed-Solomon calls on the R words, one sync, and at most one
+    mvn_lstm_maml_train_trials_f32 and one mvn_lstm_train_trials_f32 call.  MAML=True, window_size > 1 and words longer than 256
+    go trial after trial through harness.eval_by_word (its autograd routes); weights_init='random' raises ValueError (the LSTM
+    path re-initialises from torch's global generator, so a trial is not replayable on its own: run harness.eval_by_word).
+    cohorts is accepted and ignored for an LSTM bank: a training launch takes hundreds of milliseconds, the host work of a step
+    is not worth hiding behind it."""
+    from .lstm_trials import LSTMTrialBank
+
     R, N = rx.shape[0], rx.shape[1]
     if R != bank.R or len(draws) != R or tx.shape[0] != R:
         raise ValueError("tx [R, N, K], rx [R, N, K + 8 n_symbols], one TrialDraws and one bank row per trial")
@@ -229,6 +241,13 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
         if ib[0].shape != ib[1].shape or ib[0].shape[0] != R or ib[0].shape[2] != rx.shape[2]:
             raise ValueError("initial_buffer = (tx_codewords, rx_words), each [W0, T] or [R, W0, T]")
         initial_buffer = ib
+    if isinstance(bank, LSTMTrialBank):
+        from . import lstm_trials
+
+        return lstm_trials.eval_by_word(bank, tx, rx, n_symbols, subframes_in_frame, draws, self_supervised, self_supervised_iterations,
+                                        ser_thresh, online_meta, meta_lr, MAML, window_size, meta_train_iterations, meta_j_num,
+                                        meta_subframes, meta_style_online_training, weights_init, meta_training_weights, record,
+                                        initial_buffer)
     if (bank.optimizer_type != "Adam" and online_meta) or bank.n_states != 16:
         return _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, initial_buffer,
                                     dict(self_supervised=self_supervised, self_supervised_iterations=self_supervised_iterations,
