@@ -52,7 +52,7 @@ typedef void *mvn_stream_t; /* hipStream_t */
 
 #define MVN_E_BARRIER (-7)   /* (status words only) a training launch abandoned its device-wide barrier */
 
-#define MVN_ABI_VERSION 6 /* 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
+#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
 
 /* ABI version of the loaded library (== MVN_ABI_VERSION). */
 int mvn_version(void);
@@ -372,6 +372,27 @@ int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int6
                            float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld, float *label_word,
                            int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R, int32_t T, int32_t nsym,
                            int32_t pilot, int32_t S, mvn_stream_t stream);
+
+/*
+ * The two block steps above with the detected word taken from the TRACED-BACK Viterbi path instead of the reference's running
+ * argmin: same arguments, same validation and return codes, same outputs, one launch.  On a data step
+ *   dec is bit-identical to mvn_vnet_decode_surv_f32 / mvn_va_decode_surv_f32 followed by mvn_traceback_f32 (survivor = torch.min's
+ *   index, NaN when either candidate is NaN; the walk starts at torch.argmin of the final metric, a NaN counting as minimal;
+ *   dec[t] = the least-significant bit of the path's state before stage t),
+ *   msg, nerr, enc, label_word and labels are bit-identical to mvn_rs_decode_bits_f32 / mvn_rs_encode_bits_f32 (and the label
+ *   rule and calculate_states above) applied to that dec.
+ * The survivors never leave the chip.  The pilot step detects nothing: it IS the pilot step of the entry points above (no dec
+ * or msg, nerr = 0, enc = label_word = RS-encode(tx)).
+ */
+int mvn_vnet_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                  const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                  float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                  float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                  int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+int mvn_va_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
 
 /* The MVN_* environment switches (A/B variants of the kernels) are read once per process; a caller that
  * changes them afterwards (the test-suite does) calls this to have them read again. */

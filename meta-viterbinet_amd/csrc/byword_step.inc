@@ -242,3 +242,65 @@ __global__ __launch_bounds__(64) void byword_step_va_kernel(
     wave_lds_fence();
     byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, pilot);
 }
+
+// ---- The block step on the TRACED-BACK PATH (mvn_vnet_byword_step_path_f32 / mvn_va_byword_step_path_f32).  The steps above feed
+// the codec with the reference's running-argmin decisions (quirk Q1: symbol t is decided before stage t is absorbed); these feed
+// it with the textbook maximum-likelihood word -- the survivors of mvn_*_decode_surv_f32 walked back as mvn_traceback_f32 walks
+// them -- and change nothing else: the survivor words of the block stay in LDS (2 B per symbol, vnet16_common.inc's per-lane form),
+// one wave walks them from registers and carries on into byword_codec with the path's bits in sh.dbits.
+template <int NS>
+struct PathStepShared : StepShared<NS> {
+    __attribute__((aligned(16))) unsigned short surv[kCoopMaxT];
+    float fm[16];  // the final path metric, logical state order
+};
+
+template <int NS>
+__global__ __launch_bounds__(64 * kCoopWaves, 4) void byword_path_step_kernel(
+    const float *__restrict__ rx, int64_t rx_ld, const float *__restrict__ tx, int64_t tx_ld, const float *__restrict__ W1,
+    const float *__restrict__ b1, const float *__restrict__ W2, const float *__restrict__ b2, const float *__restrict__ W3,
+    const float *__restrict__ b3, WeightStrides ws, float *__restrict__ dec, int64_t dec_ld, float *__restrict__ msg,
+    int64_t msg_ld, float *__restrict__ enc, int64_t enc_ld, float *__restrict__ label_word, int64_t lw_ld,
+    int *__restrict__ labels, int64_t lab_ld, int *__restrict__ nerr_out, int T, int nsym) {
+    __shared__ PathStepShared<NS> sh;
+    constexpr bool kClosedForm = NS <= 2;
+    const int64_t r = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int k = (T >> 3) - nsym;
+    gf_load(&sh.gf);
+    {
+        const float *txb = tx + r * tx_ld;
+        for (int p = blockDim.x - 1 - threadIdx.x; p < k; p += blockDim.x) sh.txrow[p] = (unsigned char)pack_byte(txb + 8 * p);
+    }
+    float m_unused;
+    const int role = coop_detect_block<false, true>(rx + r * rx_ld, W1 + r * ws.s[0], b1 + r * ws.s[1], W2 + r * ws.s[2],
+                                                    b2 + r * ws.s[3], W3 + r * ws.s[4], b3 + r * ws.s[5], nullptr, T, &m_unused,
+                                                    [](int, float, bool) {}, sh.surv, sh.fm);
+    if (role != kCoopDecided) return;  // the wave that formed the survivors walks them back and carries on with the codec
+    path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
+    if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
+    wave_lds_fence();
+    byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, 0);
+}
+
+template <int NS>
+__global__ __launch_bounds__(64) void byword_path_step_va_kernel(
+    const float *__restrict__ rx, int64_t rx_ld, const float *__restrict__ tx, int64_t tx_ld, const float *__restrict__ priors,
+    int64_t Bp, float *__restrict__ dec, int64_t dec_ld, float *__restrict__ msg, int64_t msg_ld, float *__restrict__ enc,
+    int64_t enc_ld, float *__restrict__ label_word, int64_t lw_ld, int *__restrict__ labels, int64_t lab_ld,
+    int *__restrict__ nerr_out, int T, int nsym) {
+    __shared__ PathStepShared<NS> sh;
+    constexpr bool kClosedForm = NS <= 2;
+    const int64_t r = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int k = (T >> 3) - nsym;
+    gf_load(&sh.gf);
+    {
+        const float *txb = tx + r * tx_ld;
+        for (int p = lane; p < k; p += 64) sh.txrow[p] = (unsigned char)pack_byte(txb + 8 * p);
+    }
+    va16_tile_block_surv(rx + r * rx_ld, priors + (r % Bp) * 16, T, sh.surv, sh.fm);
+    path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
+    if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
+    wave_lds_fence();
+    byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, 0);
+}

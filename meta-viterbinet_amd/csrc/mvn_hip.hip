@@ -1569,11 +1569,12 @@ int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_
     return MVN_OK;
 }
 
-int mvn_vnet_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
-                             const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
-                             float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
-                             float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
-                             int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+// both decision rules of the ViterbiNet block step: path = the traced-back word (data steps only; a pilot detects nothing)
+static int vnet_byword_step(bool path, const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                            const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                            float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                            float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                            int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
     if (S != 16) return MVN_E_STATES;  // the fused step exists for the 16-state detector
     if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
     const int K = T - 8 * nsym;
@@ -1594,16 +1595,48 @@ int mvn_vnet_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, in
                            tx_ld, W1, b1, W2, b2, W3, b3, ws, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,   \
                            labels, lab_ld, nerr, T, nsym, pilot);                                                       \
     } while (0)
-    if (nsym <= 2) MVN_STEP_LAUNCH(2);
-    else MVN_STEP_LAUNCH(8);
+#define MVN_PATH_STEP_LAUNCH(NS)                                                                                         \
+    do {                                                                                                                \
+        int e = ensure_dynamic_lds((const void *)byword_path_step_kernel<NS>, (size_t)(kCoopMaxT / 16 * 1024));          \
+        if (e) return e;                                                                                                \
+        hipLaunchKernelGGL((byword_path_step_kernel<NS>), dim3((unsigned)R), dim3(64 * kCoopWaves), dyn, st, rx, rx_ld,  \
+                           tx, tx_ld, W1, b1, W2, b2, W3, b3, ws, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word,     \
+                           lw_ld, labels, lab_ld, nerr, T, nsym);                                                       \
+    } while (0)
+    if (path && !pilot) {
+        if (nsym <= 2) MVN_PATH_STEP_LAUNCH(2);
+        else MVN_PATH_STEP_LAUNCH(8);
+    } else {
+        if (nsym <= 2) MVN_STEP_LAUNCH(2);
+        else MVN_STEP_LAUNCH(8);
+    }
+#undef MVN_PATH_STEP_LAUNCH
 #undef MVN_STEP_LAUNCH
     return (int)hipGetLastError();
 }
 
-int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
-                           float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld, float *label_word,
-                           int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R, int32_t T, int32_t nsym,
-                           int32_t pilot, int32_t S, mvn_stream_t stream) {
+int mvn_vnet_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                             const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                             float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                             float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                             int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return vnet_byword_step(false, rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
+                            label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+}
+
+int mvn_vnet_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                  const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                  float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                  float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                  int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return vnet_byword_step(true, rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
+                            label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+}
+
+static int va_byword_step(bool path, const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors,
+                          int64_t Bp, float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                          float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R, int32_t T,
+                          int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
     if (S != 16) return MVN_E_STATES;  // the fused step exists for the 16-state detectors
     if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
     const int K = T - 8 * nsym;
@@ -1614,6 +1647,15 @@ int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int6
     if (R == 0) return MVN_OK;
     if (!tx || (!pilot && (!rx || !state_priors))) return MVN_E_NULL;
     hipStream_t st = (hipStream_t)stream;
+    if (path && !pilot) {
+        if (nsym <= 2)
+            hipLaunchKernelGGL((byword_path_step_va_kernel<2>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors,
+                               Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym);
+        else
+            hipLaunchKernelGGL((byword_path_step_va_kernel<8>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors,
+                               Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym);
+        return (int)hipGetLastError();
+    }
     if (nsym <= 2)
         hipLaunchKernelGGL((byword_step_va_kernel<2>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec,
                            dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym, pilot);
@@ -1621,6 +1663,22 @@ int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int6
         hipLaunchKernelGGL((byword_step_va_kernel<8>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec,
                            dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym, pilot);
     return (int)hipGetLastError();
+}
+
+int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                           float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld, float *label_word,
+                           int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R, int32_t T, int32_t nsym,
+                           int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return va_byword_step(false, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,
+                          labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+}
+
+int mvn_va_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return va_byword_step(true, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,
+                          labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
 }
 
 void mvn_reload_switches(void) { load_switches(); }

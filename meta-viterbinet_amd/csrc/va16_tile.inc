@@ -72,6 +72,56 @@ __device__ __forceinline__ float va16_tile_block(const float *__restrict__ yb, c
     return m;
 }
 
+// The same sweep keeping the SURVIVORS instead of the running decisions (the by-word step's traced-back decision, byword_step.inc):
+// the survivor words of the previous tile (surv16_tile_store, from its recorded metrics + costs) take the decisions' place between
+// the phases; afterwards surv_words[0 .. T) hold every step's word and fm[16] the final metric in logical state order (both LDS,
+// written and fenced by the calling wave).  Same recurrence, same NaN rule for non-finite priors.
+__device__ __forceinline__ void va16_tile_block_surv(const float *__restrict__ yb, const float *__restrict__ prior_row, int T,
+                                                     unsigned short *surv_words, float *fm) {
+    const int lane = threadIdx.x & 63;
+    const int j = lane & 15, q = lane >> 4;
+    int ulog[4];
+    float pr[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        ulog[r] = logical_state(j, r);
+        pr[r] = prior_row[ulog[r]];
+    }
+    const bool strict = __any(needs_strict_min(pr[0]) | needs_strict_min(pr[1]) | needs_strict_min(pr[2]) | needs_strict_min(pr[3]));
+    const int row_time = row_time_of(q);
+    float m = 0.0f;  // va_detector.py:84
+
+    float ynext[4], pa[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // pa: recorded metric + cost of the previous tile's steps
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ynext[r] = yb[row_time + r < T ? row_time + r : T - 1];
+    for (int tu = 0; tu < T; tu += 16) {
+        const int nsteps = T - tu < 16 ? T - tu : 16;
+        float cost[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            cost[r] = va_cost(ynext[r], pr[r]);
+            const int tn = tu + 16 + row_time + r;
+            ynext[r] = yb[tn < T ? tn : T - 1];
+        }
+        float mrec[4];
+        mrec[0] = mrec[1] = mrec[2] = mrec[3] = 0.0f;
+        auto sweep_tile = [&](auto full, auto strict_c) {
+            constexpr bool F = decltype(full)::value, ST = decltype(strict_c)::value;
+            sweep16_tile<F, ST, false>(m, cost, mrec, nsteps, 0, q, [&](auto ph) {
+                if (decltype(ph)::value == 1 && tu > 0) surv16_tile_store(pa, ulog, lane, surv_words + tu - 16);
+            });
+        };
+        if (strict) sweep_tile(std::false_type{}, std::true_type{});
+        else if (nsteps == 16) sweep_tile(std::true_type{}, std::false_type{});
+        else sweep_tile(std::false_type{}, std::false_type{});
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pa[r] = mrec[r] + cost[r];
+    }
+    surv16_tile_store(pa, ulog, lane, surv_words + (((T - 1) >> 4) << 4));
+    if (q == 0) fm[logical_state(j, T & 3)] = m;
+    wave_lds_fence();
+}
+
 // ---- The same detector with the two jobs of a block on different waves (round 5; BASELINE configs[0]: 100 blocks x 1000).
 // A lone wave issues in order, one vector instruction per ~4.5 cycles: of the ~180 instructions a 16-step tile costs va16_tile_block,
 // 32 are the recurrence (v_add_f32 + v_min_f32_dpp per step) and 100 are the four decision reductions -- the block's 93 cycles per

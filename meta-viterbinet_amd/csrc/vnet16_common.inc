@@ -521,3 +521,81 @@ __device__ __forceinline__ float decide4(const float (&rec)[4], const int (&ulog
     const int d2 = decide16<2, STRICT>(rec[2], ulog[2]), d3 = decide16<3, STRICT>(rec[3], ulog[3]);
     return (float)(jt == 0 ? d0 : jt == 1 ? d1 : jt == 2 ? d2 : d3);
 }
+
+// ---- Survivors of the in-place sweep and the walk back along them (the by-word step's traced-back decision, byword_step.inc).
+// The step at phase RHO leaves min(a, a[partner]) in both lanes of a pair, a = metric before the step + branch cost; the pair's
+// logical states before the step are 2 s and 2 s + 1, the predecessors (j = 0, 1) of the states s and s + 8 it holds afterwards.
+// torch.min's index (acs_block's argmin_j, what mvn_*_decode_surv_f32 stores) is j = 1 iff a[2 s + 1] < a[2 s], or a[2 s + 1] is NaN
+// and a[2 s] is not.  Kept here per PHYSICAL lane: did the lane's new metric come from its partner?  Exact in either form of the
+// sweep (the recorded metrics are the oracle's) and off its chain: one add, one DPP move and two compares per step.
+template <int RHO>
+__device__ __forceinline__ bool surv_from_partner(float a, int ulog_rho) {
+    const float ap = RHO == 0 ? dpp_f32<MVN_DPP_XOR1>(a) : RHO == 1 ? dpp_f32<MVN_DPP_XOR2>(a)
+                   : RHO == 2 ? dpp_f32<MVN_DPP_XOR7>(a) : dpp_f32<MVN_DPP_XOR8>(a);
+    const bool odd_wins = !((ulog_rho & 1 ? a : ap) >= (ulog_rho & 1 ? ap : a)) && (ulog_rho & 1 ? ap == ap : a == a);
+    return (ulog_rho & 1) != 0 ? !odd_wins : odd_wins;
+}
+// The survivor words of one 16-step tile from a[r] = rec[r] + cost[r] of sweep16_tile (all 64 lanes): word[t] bit p = lane p of the
+// row that swept step t took its partner's candidate.  Lane q < 4 stores the four words of row q's steps, tile_words[row_time_of(q) ..].
+__device__ __forceinline__ void surv16_tile_store(const float (&a)[4], const int (&ulog)[4], int lane, unsigned short *tile_words) {
+    const unsigned long long b0 = __ballot(surv_from_partner<0>(a[0], ulog[0])), b1 = __ballot(surv_from_partner<1>(a[1], ulog[1]));
+    const unsigned long long b2 = __ballot(surv_from_partner<2>(a[2], ulog[2])), b3 = __ballot(surv_from_partner<3>(a[3], ulog[3]));
+    if (lane < 4) {
+        const int sh = 16 * lane;
+        const unsigned lo = (unsigned)((b0 >> sh) & 0xffffu) | ((unsigned)((b1 >> sh) & 0xffffu) << 16);
+        const unsigned hi = (unsigned)((b2 >> sh) & 0xffffu) | ((unsigned)((b3 >> sh) & 0xffffu) << 16);
+        *reinterpret_cast<uint2 *>(tile_words + row_time_of(lane)) = make_uint2(lo, hi);
+    }
+}
+// The walk, by every lane of ONE wave alike (uniform addresses: LDS broadcasts): from the first minimal final metric (torch.argmin, a
+// NaN counting as minimal; fm[] in logical order) back along words[0 .. T), T % 8 == 0, eight steps per 16-byte fetch and the fetches
+// of the next 32 steps requested before the walk of these; the lane that holds the path's state before step t is
+// p_t = p_{t+1} ^ (word[t] bit p_{t+1} ? partner mask of phase t % 4 : 0), and bits[t] = sigma_t & 1 = coordinate t % 4 of p_t in
+// logical_state's basis.  Lane e of each 32 steps stores bit e: dbits (LDS, one byte per symbol) and dec (may be null).
+__device__ __forceinline__ void path16_walk(const unsigned short *words, const float *fm, int T, int lane, unsigned char *dbits,
+                                            float *__restrict__ dec) {
+    int s = 0;
+    float mv = fm[0];
+    if (mv == mv) {
+        for (int k = 1; k < 16; ++k) {
+            const float x = fm[k];
+            if (!(x >= mv)) {
+                mv = x;
+                s = k;
+                if (x != x) break;
+            }
+        }
+    }
+    int p = __builtin_ctzll(__ballot(lane < 16 && logical_state(lane, T & 3) == s));
+    const uint4 *pieces = reinterpret_cast<const uint4 *>(words);
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    uint4 cur[4], nxt[4];
+    int top = (T >> 3) - 1;  // the piece of the last eight steps
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cur[k] = top - k >= 0 ? pieces[top - k] : zero;
+    for (; top >= 0; top -= 4) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) nxt[k] = top - 4 - k >= 0 ? pieces[top - 4 - k] : zero;
+        unsigned path = 0;  // bit 8 (3 - k) + e: symbol 8 (top - k) + e
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned dw[4] = {cur[k].x, cur[k].y, cur[k].z, cur[k].w};
+#pragma unroll
+            for (int e = 7; e >= 0; --e) {
+                const unsigned w = dw[e >> 1] >> (16 * (e & 1));
+                const int mask = (e & 3) == 0 ? 1 : (e & 3) == 1 ? 2 : (e & 3) == 2 ? 7 : 8;
+                p ^= ((w >> p) & 1u) ? mask : 0;
+                const int bit = (e & 3) == 0 ? (p ^ (p >> 2)) & 1 : (e & 3) == 1 ? ((p >> 1) ^ (p >> 2)) & 1 : (p >> ((e & 3))) & 1;
+                path |= (unsigned)bit << (8 * (3 - k) + e);
+            }
+        }
+        const int t = 8 * (top - 3) + lane;  // (pieces below 0 walked zeros: their bits are not stored)
+        if (lane < 32 && t >= 0) {
+            const int bit = (path >> lane) & 1;
+            dbits[t] = (unsigned char)bit;
+            if (dec) dec[t] = (float)bit;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
+    }
+}

@@ -22,13 +22,19 @@ constexpr int kCoopMaxBlocks = 768;   // three rounds of one workgroup per CU; a
 // 16-symbol tile with the decision of symbol tdec (live = inside the block).  Returns the calling wave's role: kCoopIdle
 // (waves 2..15: nothing left to do), kCoopSwept (wave 0: *m_out = the block's final path metric, in its row-0 lanes),
 // kCoopDecided (wave 1: every sink call has been made).
+// SURV (the by-word step's traced-back decision, byword_step.inc): the running-argmin decisions are not taken and sink is never
+// called.  Wave 0 hands over a = recorded metric + branch cost of its four steps instead of the recorded metrics (four adds per tile
+// off the chain, the same sums the steps formed), wave 1 turns them into the tile's survivor words surv_words[16 tile ..]
+// (surv16_tile_store) and, once wave 0 has left the final metric in fm[16] (logical state order), returns kCoopDecided: the words of
+// steps 0 .. T - 1 and fm are then visible to it.
 enum { kCoopIdle = 0, kCoopSwept = 1, kCoopDecided = 2 };
-template <bool WRITE_LOGITS, class Sink>
+template <bool WRITE_LOGITS, bool SURV = false, class Sink>
 __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, const float *__restrict__ W1,
                                                  const float *__restrict__ b1, const float *__restrict__ W2,
                                                  const float *__restrict__ b2, const float *__restrict__ W3,
                                                  const float *__restrict__ b3, float *__restrict__ logits_b, int T,
-                                                 float *m_out, Sink sink) {
+                                                 float *m_out, Sink sink, unsigned short *surv_words = nullptr,
+                                                 float *fm = nullptr) {
     constexpr int S = 16;
     __shared__ int s_swept;  // tiles whose recorded metrics wave 0 has handed over
     __shared__ Vnet16Image img;              // the weights (vnet16_common.inc)
@@ -96,10 +102,18 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
             if (strict) sweep16_tile<false, true, false>(m, cost, mrec, nsteps, 0, q);  // torch.min's NaN rule (vnet16_common.inc)
             else if (nsteps == 16) sweep16_tile<true, false, false>(m, cost, mrec, nsteps, 0, q);
             else sweep16_tile<false, false, false>(m, cost, mrec, nsteps, 0, q);
+            if (SURV) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mrec[r] += cost[r];
+            }
             reinterpret_cast<float4 *>(costs + tu * S)[lane] = make_float4(mrec[0], mrec[1], mrec[2], mrec[3]);
             __hip_atomic_store(&s_swept, tile + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         *m_out = m;
+        if (SURV) {
+            if (q == 0) fm[logical_state(j, T & 3)] = m;
+            __hip_atomic_store(&s_swept, tiles + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
         return kCoopSwept;
     }
     for (int tile = 0; tile < tiles; ++tile) {
@@ -109,8 +123,16 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
         while (__hip_atomic_load(&s_swept, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= tile) __builtin_amdgcn_s_sleep(1);
         const float4 mr4 = reinterpret_cast<const float4 *>(costs + tu * S)[lane];
         const float mrec[4] = {mr4.x, mr4.y, mr4.z, mr4.w};
+        if (SURV) {
+            surv16_tile_store(mrec, ulog, lane, surv_words + tu);
+            continue;
+        }
         const float mydec = strict ? decide4<true>(mrec, ulog, j) : decide4<false>(mrec, ulog, j);
         if (j < 4) sink(tdec, mydec, row_time + j < nsteps);
+    }
+    if (SURV) {
+        while (__hip_atomic_load(&s_swept, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= tiles) __builtin_amdgcn_s_sleep(1);
+        wave_lds_fence();  // (the words are this wave's own LDS writes)
     }
     return kCoopDecided;
 }

@@ -90,17 +90,46 @@ def _gpu_counter(detected: torch.Tensor, tx: torch.Tensor, rows: Optional[torch.
     return _metrics.count_errors(detected, tx, rows)
 
 
+DECISIONS = ("running", "path")
+
+
+def _check_decision(decision: str, detector=None) -> None:
+    """decision: 'running' = the reference's running argmin (quirk Q1, symbol t decided before stage t is absorbed), 'path' = the
+    traced-back maximum-likelihood word (detector.viterbi_path); the LSTM detectors have no trellis to trace back."""
+    if decision not in DECISIONS:
+        raise ValueError(f"decision must be one of {DECISIONS}, got {decision!r}")
+    if decision == "path" and not hasattr(detector, "viterbi_path"):
+        raise ValueError(f"decision='path' needs a Viterbi / ViterbiNet detector ({type(detector).__name__} has no viterbi_path)")
+
+
+def _detect(detector: Callable, y: torch.Tensor, snr: float, gamma: float, decision: str = "running", count: int = None,
+            pass_count: bool = False) -> torch.Tensor:
+    """detector(y, 'val', snr, gamma[, count]), or its traced-back path for decision='path'."""
+    if decision == "path":
+        from .detectors import VADetector
+
+        if not isinstance(detector, VADetector):  # ViterbiNet's path takes the word only (its forward ignores snr, gamma, count)
+            return detector.viterbi_path(y)
+        return detector.viterbi_path(y, snr, gamma, count) if pass_count else detector.viterbi_path(y, snr, gamma)
+    return detector(y, "val", snr, gamma, count) if pass_count else detector(y, "val", snr, gamma)
+
+
 def eval_counters(detector: Callable, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma: float,
                   rows: Optional[torch.Tensor] = None, counter: Callable = _gpu_counter,
-                  group=None, reduce: bool = True, n_symbols: int = 0, rs_decoder: Callable = rs_decode) -> torch.Tensor:
+                  group=None, reduce: bool = True, n_symbols: int = 0, rs_decoder: Callable = rs_decode,
+                  decision: str = "running") -> torch.Tensor:
     """One Monte-Carlo point on THIS rank's rows: detect -> [RS decode] -> count -> (optionally) all-reduce.
     `tx`/`rx` are the rank-local shards; `rows` are local row indices counted (None = all).
     n_symbols > 0 = the reference's use_ecc path (trainer.py:234-236): detected words are RS-decoded (on the
     device) before they are compared with the transmitted message bits.
+    decision='path': the traced-back word (detector.viterbi_path) is counted instead of the running-argmin decisions.
     Returns int64[4] counters (global sums when reduce=True and a process group is up)."""
+    _check_decision(decision, detector)
     if n_symbols > 0:
-        detected = detector(rx, "val", snr, gamma)
+        detected = _detect(detector, rx, snr, gamma, decision)
         counters = counter(rs_decoder(detected, n_symbols)[:, : tx.shape[1]], tx, rows)
+    elif decision == "path":
+        counters = counter(_detect(detector, rx, snr, gamma, decision)[:, : tx.shape[1]], tx, rows)
     elif counter is _gpu_counter and getattr(detector, "n_states", None) == 16 and hasattr(detector, "val_count"):
         counters = detector.val_count(rx, tx, rows)  # decode + count in one launch, decisions never stored
     else:
@@ -113,10 +142,10 @@ def eval_counters(detector: Callable, tx: torch.Tensor, rx: torch.Tensor, snr: f
 
 def single_eval_at_point(detector: Callable, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma: float,
                          rows: Optional[torch.Tensor] = None, counter: Callable = _gpu_counter,
-                         group=None, n_symbols: int = 0) -> Tuple[float, float, torch.Tensor]:
+                         group=None, n_symbols: int = 0, decision: str = "running") -> Tuple[float, float, torch.Tensor]:
     """trainer.py:222-241 without the data draw: detect, optional RS decode (n_symbols > 0 = use_ecc), error
     rates over the data rows.  Returns (ser, fer, counters); the reference returns ser only (:238-241)."""
-    counters = eval_counters(detector, tx, rx, snr, gamma, rows, counter, group, n_symbols=n_symbols)
+    counters = eval_counters(detector, tx, rx, snr, gamma, rows, counter, group, n_symbols=n_symbols, decision=decision)
     ser, fer = _metrics.rates_from_counters(counters)
     return ser, fer, counters
 
@@ -124,7 +153,7 @@ def single_eval_at_point(detector: Callable, tx: torch.Tensor, rx: torch.Tensor,
 def sharded_eval(detector: Callable, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma: float,
                  rows: Optional[torch.Tensor] = None, counter: Callable = _gpu_counter, group=None,
                  rank: Optional[int] = None, world: Optional[int] = None, n_symbols: int = 0,
-                 rs_decoder: Callable = rs_decode) -> Tuple[float, float, torch.Tensor]:
+                 rs_decoder: Callable = rs_decode, decision: str = "running") -> Tuple[float, float, torch.Tensor]:
     """Same point, but given the FULL (tx, rx) on every rank: each rank takes its contiguous row shard
     (shard_range), maps the global `rows` filter into it, and the counters are all-reduced."""
     if rank is None:
@@ -139,7 +168,7 @@ def sharded_eval(detector: Callable, tx: torch.Tensor, rx: torch.Tensor, snr: fl
         local_rows = r.to(tx.device)
     if hi > lo:
         counters = eval_counters(detector, tx[lo:hi], rx[lo:hi], snr, gamma, local_rows, counter, group, reduce=False,
-                                 n_symbols=n_symbols, rs_decoder=rs_decoder)
+                                 n_symbols=n_symbols, rs_decoder=rs_decoder, decision=decision)
     else:
         counters = torch.zeros(4, dtype=torch.int64, device=tx.device)
     if dist.is_available() and dist.is_initialized():
@@ -213,7 +242,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
                  MAML: bool = True, window_size: int = 1, meta_train_iterations: int = 20, meta_j_num: int = 10,
                  meta_subframes: int = 5, meta_style_online_training: bool = False,
                  graphed_meta: bool = True, hip_meta: bool = True, initial_buffer=None, weights_init: str = "last_frame",
-                 meta_training_weights=None, draws=None, fused_step: bool = True, observer=None) -> np.ndarray:
+                 meta_training_weights=None, draws=None, fused_step: bool = True, observer=None,
+                 decision: str = "running") -> np.ndarray:
     """Sequential per-block online evaluation: counterpart of Trainer.eval_by_word (trainer.py:267-354).  Everything but the
     control flow stays on the GPU:
         for every block k:  detect (B=1)  ->  data block: RS decode, ser, RS re-encode | pilot: encode the known word
@@ -244,13 +274,18 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     (meta_lstm_trainer.py): meta_detector defaults to MetaLSTMDetector(), every meta update is ONE maml_training call (first order
     with window_size 1: one launch of mvn_lstm_maml_train_f32; otherwise the trainer's autograd route), graphed_meta does not apply,
     weights_init='random' re-initialises the detector in place like LSTMDetector() and resets the optimizer, and
-    meta_style_online_training=True is MetaLSTMTrainer.online_training."""
+    meta_style_online_training=True is MetaLSTMTrainer.online_training.
+    decision: 'running' (default) detects like the reference, by the running argmin (quirk Q1); 'path' detects every block by the
+    traced-back maximum-likelihood word -- in the one-launch step where it applies (mvn_vnet_byword_step_path_f32 /
+    mvn_va_byword_step_path_f32), else by detector.viterbi_path in the separate launches -- and everything downstream (RS
+    decode, ser, the buffered label word, every update branch) runs unchanged on it.  Not for the LSTM detectors (ValueError)."""
     import copy
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
 
     from .lstm import LSTMDetector, LSTMMetaTrainer, LSTMOnlineTrainer, MetaLSTMDetector
 
+    _check_decision(decision, detector)
     lstm_meta = False  # the Meta-LSTM curve: an LSTMDetector meta-learned by an LSTMMetaTrainer (meta_lstm_trainer.py)
     if isinstance(detector, (LSTMDetector, MetaLSTMDetector)):
         if online_meta:
@@ -280,7 +315,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
             for count in range(N):
                 if count % subframes_in_frame != 0:
                     _byword_step(detector, rx[count:count + 1], tx[count:count + 1], n_symbols, False, nerr[count:count + 1],
-                                 outputs=False, gamma=gamma, count=count if pass_count else None)
+                                 outputs=False, gamma=gamma, count=count if pass_count else None, decision=decision)
             e = nerr.cpu().numpy()
             data = np.arange(N) % subframes_in_frame != 0
             ser_by_word[data] = _metrics.ser_from_errors(e[data], K)  # the reference's value bit for bit (metrics.py:13-16)
@@ -290,7 +325,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
             if count % subframes_in_frame == 0:
                 continue
             received_word = rx[count:count + 1]
-            detected_word = detector(received_word, "val", snr, gamma, count) if pass_count else detector(received_word, "val", snr, gamma)
+            detected_word = _detect(detector, received_word, snr, gamma, decision, count, pass_count)
             _metrics.count_errors(rs_decode(detected_word, n_symbols), tx[count:count + 1], None, counters[count])
         c = counters.cpu().numpy()
         data = c[:, 1] > 0
@@ -347,7 +382,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
         seen = {"count": count, "meta": None, "trained": False, "batch_idx": None} if observer is not None else None
         status_word = None
         if step_labels:  # ONE launch: detect, RS decode, error count, re-encode, the word to buffer and its states
-            label_word, label_states = _byword_step(detector, received_word, transmitted_word, n_symbols, pilot, nerr1, labels=True)
+            label_word, label_states = _byword_step(detector, received_word, transmitted_word, n_symbols, pilot, nerr1, labels=True,
+                                                     decision=decision)
             if sync_words is not None:
                 n_err, status_word = sync_words.tolist()
             else:
@@ -357,12 +393,12 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
                 ser_by_word[count] = ser
         elif fused:  # ONE launch: detect, RS decode, error count, re-encode (pilot: encode the known word)
             detected_word, encoded_word = _byword_step(detector, received_word, transmitted_word, n_symbols, pilot, nerr1,
-                                                       gamma=gamma, count=count if pass_count else None)
+                                                       gamma=gamma, count=count if pass_count else None, decision=decision)
             ser = 0.0 if pilot else float(_metrics.ser_from_errors(int(nerr1.item()), K))  # calculate_error_rates (:301)
             if not pilot:
                 ser_by_word[count] = ser
         else:
-            detected_word = detector(received_word, "val", snr, gamma, count) if pass_count else detector(received_word, "val", snr, gamma)
+            detected_word = _detect(detector, received_word, snr, gamma, decision, count, pass_count)
             if not pilot:
                 decoded_word = rs_decode(detected_word, n_symbols)
                 ser = float(_metrics.ser_from_errors(int((decoded_word != transmitted_word).sum().item()), K))  # calculate_error_rates (:301)
@@ -480,16 +516,20 @@ def _fused_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: 
 
 
 def _byword_step(detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, n_symbols: int, pilot: bool,
-                 nerr: torch.Tensor, outputs: bool = True, gamma: float = None, count: int = None, labels: bool = False):
+                 nerr: torch.Tensor, outputs: bool = True, gamma: float = None, count: int = None, labels: bool = False,
+                 decision: str = "running"):
     """One block of eval_by_word in one launch (trainer.py:292-316): returns (detected_word, encoded_word) [1, T]; the
     block's bit-error count goes to nerr[0] (device int32).  On a pilot the detection is skipped (never used) and
     detected_word is None.  outputs=False: the error count only (no words are stored, the re-encoding is skipped).
     gamma / count: what VADetector.forward takes to find the word's channel (count None: the detector's single table row).
     labels=True (ViterbiNet): returns (label_word [1, T], states int32 [1, T]) instead -- the word the reference pushes into its
     buffer (:322-324: the detected word if it had bit errors, else the re-encoded one) and its trellis states, both chosen and
-    computed by the kernel."""
+    computed by the kernel.  decision='path': the same step on the traced-back word (the *_path_f32 entry points)."""
     from . import _lib
     from .detectors import VADetector
+
+    va_name, vnet_name = (("mvn_va_byword_step_path_f32", "mvn_vnet_byword_step_path_f32") if decision == "path" else
+                          ("mvn_va_byword_step_f32", "mvn_vnet_byword_step_f32"))
 
     rxw, txw = _lib.f32c(received_word), _lib.f32c(transmitted_word)
     T, K = rxw.shape[1], txw.shape[1]
@@ -500,25 +540,25 @@ def _byword_step(detector, received_word: torch.Tensor, transmitted_word: torch.
         pri = detector._priors_table(rxw, gamma, "val", count)  # [W, 16] (one row when count is given)
         assert pri.shape[0] == 1  # (_fused_step_applies sends every other table to the separate launches)
         with _lib.on_device(dev):
-            rc = _lib.load().mvn_va_byword_step_f32(_lib.ptr(rxw), T, _lib.ptr(txw), K, _lib.ptr(pri), 1, _lib.ptr(det), T, None, K,
-                                                    _lib.ptr(enc), T, None, T, None, T, _lib.ptr(nerr), 1, T, n_symbols,
-                                                    1 if pilot else 0, 16, _lib.current_stream(dev))
-        _lib.check(rc, "mvn_va_byword_step_f32")
+            rc = getattr(_lib.load(), va_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, _lib.ptr(pri), 1, _lib.ptr(det), T, None, K,
+                                               _lib.ptr(enc), T, None, T, None, T, _lib.ptr(nerr), 1, T, n_symbols,
+                                               1 if pilot else 0, 16, _lib.current_stream(dev))
+        _lib.check(rc, va_name)
         return det, enc
     w = detector._params()
     if labels:
         word, states = torch.empty((1, T), dtype=torch.float32, device=dev), torch.empty((1, T), dtype=torch.int32, device=dev)
         with _lib.on_device(dev):
-            rc = _lib.load().mvn_vnet_byword_step_f32(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
-                                                      None, T, None, K, None, T, _lib.ptr(word), T, _lib.ptr(states), T,
-                                                      _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
-                                                      _lib.current_stream(dev))
-        _lib.check(rc, "mvn_vnet_byword_step_f32")
+            rc = getattr(_lib.load(), vnet_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
+                                                 None, T, None, K, None, T, _lib.ptr(word), T, _lib.ptr(states), T,
+                                                 _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
+                                                 _lib.current_stream(dev))
+        _lib.check(rc, vnet_name)
         return word, states
     with _lib.on_device(dev):
-        rc = _lib.load().mvn_vnet_byword_step_f32(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
-                                                  _lib.ptr(det), T, None, K, _lib.ptr(enc), T, None, T, None, T,
-                                                  _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
-                                                  _lib.current_stream(dev))
-    _lib.check(rc, "mvn_vnet_byword_step_f32")
+        rc = getattr(_lib.load(), vnet_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
+                                             _lib.ptr(det), T, None, K, _lib.ptr(enc), T, None, T, None, T,
+                                             _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
+                                             _lib.current_stream(dev))
+    _lib.check(rc, vnet_name)
     return det, enc
