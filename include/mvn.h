@@ -394,6 +394,42 @@ int mvn_va_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx,
                                 float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                 int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
 
+/*
+ * The path steps above with a RELIABILITY-ORDERED LIST DECODE (a Chase-type decoder judged by the trellis's own metric), one launch.
+ * (Added without a bump of MVN_ABI_VERSION, like the path steps.)  All arithmetic is fp32, every operation rounded on its own.
+ * With cost[t][s] the detector's branch cost of stage t for the state s before it (Viterbi: va_detector.py:64-68; ViterbiNet:
+ * -logit), successors of p being p >> 1 and (p >> 1) | 8, and alpha the forward sweep the detectors run:
+ *   beta_T = 0, beta_t[p] = cost[t][p] + min(beta_{t+1}[p >> 1], beta_{t+1}[(p >> 1) | 8])
+ *   delta_t = min_{s odd}(alpha_t[s] + beta_t[s]) - min_{s even}(alpha_t[s] + beta_t[s])      (the max-log LLR; its sign is dec)
+ *   rho_j   = min_{i<8} |delta_{8j+i}| for the n = T / 8 bytes, parity included; the bytes are ranked by (rho, j) ascending and
+ *             U = the first list_bytes of them
+ *   candidate 0 = the message the path step returns for dec; candidates 1 .. C(list_bytes, nsym) = for every nsym-subset of U, in
+ *             lexicographic order of rank tuples, the codeword that agrees with dec on the other n - nsym bytes (erasure filling)
+ *   M(c) = sum_t cost[t][state_t(c)], ascending t, state_t = calculate_states of the (re-)encoded candidate
+ *   choice = the candidate with the smallest M, the lowest index among equals.
+ * msg is the chosen candidate's message; nerr, enc, label_word (dec if nerr > 0 else enc) and labels follow from it as in the
+ * steps above; dec stays the traced-back word.  delta [R, >= T] (row stride delta_ld) and choice [R] may be NULL.  tx may be NULL
+ * on a data step when nerr, label_word and labels are NULL: a decoder without a genie.  The pilot step is the pilot step above
+ * (delta and choice are not written).
+ * Limits, checked before any pointer: S = 16 (else MVN_E_STATES); T a multiple of 8, 8 (nsym + 1) <= T <= 512 (costs and alpha
+ * stay in LDS, 128 B per symbol: at T = 1024 they would need 128 KB next to the ViterbiNet workgroup's 57.6 KB of weights, tiles
+ * and step state, more than a CU's 160 KB); 1 <= nsym <= 8; nsym <= list_bytes <= T / 8; C(list_bytes, nsym) <= 63 (one candidate per lane of one wavefront); else
+ * MVN_E_DIMS.
+ * Non-finite costs: candidate 0 keeps the path step's rules; the call stays memory-safe and deterministic, but which candidate is
+ * chosen is then unspecified.
+ */
+int mvn_vnet_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                  const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                  float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                  float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                  int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                  int64_t delta_ld, int32_t *choice, mvn_stream_t stream);
+int mvn_va_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                int64_t delta_ld, int32_t *choice, mvn_stream_t stream);
+
 /* The MVN_* environment switches (A/B variants of the kernels) are read once per process; a caller that
  * changes them afterwards (the test-suite does) calls this to have them read again. */
 void mvn_reload_switches(void);

@@ -62,6 +62,10 @@ SIGNATURES = {
                                       [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "mvn_va_byword_step_path_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32,
                                                    _i32, _i32, _i32, _vp]),
+    "mvn_vnet_byword_step_list_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [ctypes.POINTER(ctypes.c_int64)] +
+                                      [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mvn_va_byword_step_list_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32,
+                                                   _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "mvn_reload_switches": (None, []),
     "mvn_isi_awgn_transmit": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, ctypes.c_double, _vp, _i64, _i64,
                                              _i32, _i32, _vp]),

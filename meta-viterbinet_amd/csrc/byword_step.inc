@@ -34,87 +34,74 @@ struct StepShared {
     int s_loc[NS + 4];  // the error locator and its {length, leading zeros}, from the lane that ran Berlekamp-Massey
 };
 
-// Everything of a block step after the detection, by ONE wave (the caller's): sh.dbits holds the detected word (data step),
-// sh.txrow the transmitted message as bytes, sh.gf the tables (and sh.gen the generator polynomial when NS > 2); word r's
-// outputs as in mvn_vnet_byword_step_f32.
+// The hard decoder of a data step, by ONE wave: np.packbits of sh.dbits into sh.row (and into raw, when given: the word's bytes as
+// detected), the syndromes (left in synd, every lane alike), and the correction of the message bytes in place.
 template <int NS>
-__device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int lane, float *__restrict__ msg, int64_t msg_ld,
-                                             float *__restrict__ enc, int64_t enc_ld, float *__restrict__ label_word, int64_t lw_ld,
-                                             int *__restrict__ labels, int64_t lab_ld, int *__restrict__ nerr_out, int T, int nsym,
-                                             int pilot) {
+__device__ __forceinline__ void byword_decode_row(StepShared<NS> &sh, int lane, int n, int nsym, int (&synd)[NS + 1],
+                                                  unsigned char *raw) {
+    GfTables &gf = sh.gf;
+    int *s_loc = sh.s_loc;
+    unsigned char *row = sh.row, *dbits = sh.dbits;
+    // np.packbits of the detected word, one lane per byte; syndromes synd[i + 1] = sum_p byte_p (2^i)^(n - 1 - p)
+    // (rs_calc_syndromes, rs_decoder.py:37-47, Horner form written out), xor-reduced over the lanes
+    synd[0] = 0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) synd[i + 1] = 0;
+    for (int p = lane; p < n; p += 64) {
+        int byte = 0;
+#pragma unroll
+        for (int jb = 0; jb < 8; ++jb) byte = (byte << 1) | (dbits[8 * p + jb] & 1);
+        row[p] = (unsigned char)byte;
+        if (raw) raw[p] = (unsigned char)byte;
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+            if (i < nsym) synd[i + 1] ^= gf_mul(&gf, byte, gf_pow2(&gf, i * (n - 1 - p)));
+    }
+    int any = 0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) synd[i + 1] ^= __shfl_xor(synd[i + 1], off);
+        any |= synd[i + 1];
+    }
+    wave_lds_fence();
+    if (any) {  // wave-uniform: rs_locate_correct's three stages, the middle one spread over the lanes
+        if (lane == 0) {
+            int err_loc[NS + 2], lead;
+            const int el = rs_error_locator<NS>(&gf, synd, nsym, err_loc, lead);
+            for (int t = 0; t < el; ++t) s_loc[t] = err_loc[t];
+            s_loc[NS + 2] = el;
+            s_loc[NS + 3] = lead;
+        }
+        wave_lds_fence();
+        const int el = s_loc[NS + 2], lead = s_loc[NS + 3];
+        if ((el - lead - 1) * 2 <= nsym) {  // else "too many errors": the uncorrected systematic part (rs_main.py:31-33)
+            // rs_find_errors: position n - 1 - i errs iff the locator vanishes at 2^i; kept in the order of i
+            unsigned long long roots[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int i = lane + 64 * h;
+                roots[h] = __ballot(i < n && rs_locator_at(&gf, s_loc, el, lead, i) == 0);
+            }
+            if (lane == 0) {
+                int npos = 0, pos[NS / 2 + 1];
+                for (int h = 0; h < 2; ++h)
+                    for (unsigned long long m = roots[h]; m && npos <= NS / 2; m &= m - 1)
+                        pos[npos++] = n - 1 - (64 * h + __builtin_ctzll(m));
+                rs_forney_correct<NS>(&gf, synd, pos, npos, row, n, nsym);
+            }
+        }
+    }
+    wave_lds_fence();
+}
+
+// encode(message bytes sh.row[0 .. k)) by ONE wave: the parity bytes sh.row[k .. n)  (rs_encoder.py:7-37)
+template <int NS>
+__device__ __forceinline__ void byword_encode_row(StepShared<NS> &sh, int lane, int n, int nsym) {
     constexpr bool kClosedForm = NS <= 2;  // parity from the message's sums at 2^0, 2^1 instead of the generator polynomial
     GfTables &gf = sh.gf;
-    int *gen = sh.gen, *s_loc = sh.s_loc;
-    unsigned char *row = sh.row, *txrow = sh.txrow, *dbits = sh.dbits, *lwb = sh.lwb;
-    const int n = T >> 3, k = n - nsym;
-    // ---- one wave (the deciding wave; wave 0 on a pilot): the codec on the word's byte image
-    int nerr = 0;
-    if (!pilot) {
-        // np.packbits of the detected word, one lane per byte; syndromes synd[i + 1] = sum_p byte_p (2^i)^(n - 1 - p)
-        // (rs_calc_syndromes, rs_decoder.py:37-47, Horner form written out), xor-reduced over the lanes
-        int synd[NS + 1];
-        synd[0] = 0;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) synd[i + 1] = 0;
-        for (int p = lane; p < n; p += 64) {
-            int byte = 0;
-#pragma unroll
-            for (int jb = 0; jb < 8; ++jb) byte = (byte << 1) | (dbits[8 * p + jb] & 1);
-            row[p] = (unsigned char)byte;
-#pragma unroll
-            for (int i = 0; i < NS; ++i)
-                if (i < nsym) synd[i + 1] ^= gf_mul(&gf, byte, gf_pow2(&gf, i * (n - 1 - p)));
-        }
-        int any = 0;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) synd[i + 1] ^= __shfl_xor(synd[i + 1], off);
-            any |= synd[i + 1];
-        }
-        wave_lds_fence();
-        if (any) {  // wave-uniform: rs_locate_correct's three stages, the middle one spread over the lanes
-            if (lane == 0) {
-                int err_loc[NS + 2], lead;
-                const int el = rs_error_locator<NS>(&gf, synd, nsym, err_loc, lead);
-                for (int t = 0; t < el; ++t) s_loc[t] = err_loc[t];
-                s_loc[NS + 2] = el;
-                s_loc[NS + 3] = lead;
-            }
-            wave_lds_fence();
-            const int el = s_loc[NS + 2], lead = s_loc[NS + 3];
-            if ((el - lead - 1) * 2 <= nsym) {  // else "too many errors": the uncorrected systematic part (rs_main.py:31-33)
-                // rs_find_errors: position n - 1 - i errs iff the locator vanishes at 2^i; kept in the order of i
-                unsigned long long roots[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int i = lane + 64 * h;
-                    roots[h] = __ballot(i < n && rs_locator_at(&gf, s_loc, el, lead, i) == 0);
-                }
-                if (lane == 0) {
-                    int npos = 0, pos[NS / 2 + 1];
-                    for (int h = 0; h < 2; ++h)
-                        for (unsigned long long m = roots[h]; m && npos <= NS / 2; m &= m - 1)
-                            pos[npos++] = n - 1 - (64 * h + __builtin_ctzll(m));
-                    rs_forney_correct<NS>(&gf, synd, pos, npos, row, n, nsym);
-                }
-            }
-        }
-        wave_lds_fence();
-        for (int p = lane; p < k; p += 64) nerr += __popc((unsigned)(row[p] ^ txrow[p]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nerr += __shfl_xor(nerr, off);
-        if (msg) {
-            float *mb = msg + r * msg_ld;
-            for (int e = lane; e < 8 * k; e += 64) mb[e] = (float)((row[e >> 3] >> (7 - (e & 7))) & 1);
-        }
-    } else {
-        for (int p = lane; p < k; p += 64) row[p] = txrow[p];
-    }
-    if (lane == 0 && nerr_out) nerr_out[r] = nerr;
-    if (!enc && !label_word && !labels) return;  // (the evaluation without updates reads the error count only)
-    wave_lds_fence();
-    // encode(decoded) / encode(transmitted)  (rs_encoder.py:7-37)
+    unsigned char *row = sh.row;
+    const int k = n - nsym;
     if (kClosedForm) {
         int s0 = 0, s1 = 0;  // the message part at 2^0 and 2^1
         for (int p = lane; p < k; p += 64) {
@@ -137,9 +124,42 @@ __device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int 
             }
         }
     } else if (lane == 0) {
-        rs_append_parity<NS>(gf, gen, row, k, nsym);
+        rs_append_parity<NS>(gf, sh.gen, row, k, nsym);
     }
     wave_lds_fence();
+}
+
+// Everything of a block step after the detection, by ONE wave (the caller's): sh.dbits holds the detected word (data step),
+// sh.txrow the transmitted message as bytes, sh.gf the tables (and sh.gen the generator polynomial when NS > 2); word r's
+// outputs as in mvn_vnet_byword_step_f32.  CHOSEN (the list step, below): sh.row already holds the codeword to report.
+template <int NS, bool CHOSEN = false>
+__device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int lane, float *__restrict__ msg, int64_t msg_ld,
+                                             float *__restrict__ enc, int64_t enc_ld, float *__restrict__ label_word, int64_t lw_ld,
+                                             int *__restrict__ labels, int64_t lab_ld, int *__restrict__ nerr_out, int T, int nsym,
+                                             int pilot) {
+    unsigned char *row = sh.row, *txrow = sh.txrow, *dbits = sh.dbits, *lwb = sh.lwb;
+    const int n = T >> 3, k = n - nsym;
+    // ---- one wave (the deciding wave; wave 0 on a pilot): the codec on the word's byte image
+    int nerr = 0;
+    if (!pilot) {
+        if (!CHOSEN) {
+            int synd[NS + 1];
+            byword_decode_row<NS>(sh, lane, n, nsym, synd, nullptr);
+        }
+        for (int p = lane; p < k; p += 64) nerr += __popc((unsigned)(row[p] ^ txrow[p]));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) nerr += __shfl_xor(nerr, off);
+        if (msg) {
+            float *mb = msg + r * msg_ld;
+            for (int e = lane; e < 8 * k; e += 64) mb[e] = (float)((row[e >> 3] >> (7 - (e & 7))) & 1);
+        }
+    } else {
+        for (int p = lane; p < k; p += 64) row[p] = txrow[p];
+    }
+    if (lane == 0 && nerr_out) nerr_out[r] = nerr;
+    if (!enc && !label_word && !labels) return;  // (the evaluation without updates reads the error count only)
+    wave_lds_fence();
+    if (!CHOSEN) byword_encode_row<NS>(sh, lane, n, nsym);  // encode(decoded) / encode(transmitted)
 
     // ---- encoded word, label word (trainer.py:322-324) and its trellis states
     const bool use_detected = nerr > 0;
@@ -303,4 +323,234 @@ __global__ __launch_bounds__(64) void byword_path_step_va_kernel(
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
     wave_lds_fence();
     byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, 0);
+}
+
+// ---- The block step with a RELIABILITY-ORDERED LIST DECODE (mvn_vnet_byword_step_list_f32 / mvn_va_byword_step_list_f32).  The path
+// step above hands the hard decoder the traced-back word dec and throws the rest of the trellis away; here the branch costs
+// cost[t][s] (s = the state before stage t) and the forward metrics alpha_t[s] stay in LDS, and the wave that walked the path back
+// goes on, everything in fp32 with individually rounded operations:
+//   beta    beta_T = 0, beta_t[p] = cost[t][p] + min(beta_{t+1}[p >> 1], beta_{t+1}[(p >> 1) | 8]), one lane per state (16 lanes);
+//           alpha_t + beta_t overwrites the alpha image
+//   delta   delta_t = min_{s odd}(alpha_t[s] + beta_t[s]) - min_{s even}(...), the max-log LLR, one lane per symbol
+//   rank    rho_j = min_{i<8} |delta_{8j+i}|; the n = T / 8 bytes ordered by (rho, j); U = the first m of them
+//   cand 0  the hard decoder's message for dec (byword_decode_row, as the path step) and its parity
+//   cand c  c = 1 .. C(m, nsym), ONE PER LANE: the c-th nsym-subset of U in lexicographic order of ranks is erased in dec and filled
+//           (rs_erasure_fill)
+//   metric  M(c) = sum_t cost[t][state_t(c)] in ascending t, state_t = sum_i 2^i b[t + i] of the candidate codeword padded with zeros
+//   choice  the smallest M, the lowest index among equals; that codeword is what the rest of the step (byword_codec) reports
+// T <= kListMaxT = 512: costs and alpha take 64 B per symbol each, 64 KB at T = 512 next to the ViterbiNet workgroup's 57.6 KB of
+// weights, tiles and step state (121.6 KB of a CU's 160 KB); T = 1024 would need 128 KB, which no CU has next to them.
+// Non-finite costs: candidate 0 keeps the path step's rules; ranks, fills and the choice are then deterministic and every index stays
+// in range, but which candidate wins is not specified.
+constexpr int kListMaxT = 512;
+constexpr int kListMaxCand = 63;    // candidates 1 .. 63 next to the hard decoder's: one wave
+constexpr int kCandStride = 68;     // bytes between the candidates' codewords: 17 dwords, the lanes' byte reads spread over the banks
+
+template <int NS>
+struct ListStepShared : PathStepShared<NS> {
+    float delta[kListMaxT];
+    float rho[64];
+    __attribute__((aligned(4))) unsigned char raw[kRsRow];  // dec as bytes
+    unsigned char order[64];                                // byte positions by rank
+    __attribute__((aligned(4))) unsigned char cand[64 * kCandStride];
+};
+
+__device__ __forceinline__ int list_binom(int a, int b) {  // C(a, b), every partial product a binomial itself
+    if (b < 0 || b > a) return 0;
+    int c = 1;
+    for (int i = 1; i <= b; ++i) c = c * (a - b + i) / i;
+    return c;
+}
+
+// Everything of a list step after the walk, by ONE wave: sh.dbits = dec, cost / alpha = the [t][16] images, sh.gf / sh.gen / sh.txrow
+// as for byword_codec.  ncand = C(m, nsym).
+template <int NS>
+__device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const float *cost, float *alpha, int64_t r, int lane,
+                                                 float *__restrict__ msg, int64_t msg_ld, float *__restrict__ enc, int64_t enc_ld,
+                                                 float *__restrict__ label_word, int64_t lw_ld, int *__restrict__ labels,
+                                                 int64_t lab_ld, int *__restrict__ nerr_out, float *__restrict__ delta_out,
+                                                 int64_t delta_ld, int *__restrict__ choice_out, int T, int nsym, int m, int ncand) {
+    const int n = T >> 3;
+    // ---- beta, and alpha + beta in place: lanes 0..15, one per state (the other lanes take part in the cross-lane reads only; what
+    // they hold is never read)
+    {
+        const int s = lane & 15, src0 = s >> 1, src1 = src0 | 8;
+        const bool mine = lane < 16;
+        float beta = 0.0f;
+        float c = mine ? cost[(T - 1) * 16 + s] : 0.0f, a = mine ? alpha[(T - 1) * 16 + s] : 0.0f;
+        for (int t = T - 1; t >= 0; --t) {
+            const int tn = t > 0 ? t - 1 : 0;
+            float cn = 0.0f, an = 0.0f;
+            if (mine) {  // the next step's operands, off the chain
+                cn = cost[tn * 16 + s];
+                an = alpha[tn * 16 + s];
+            }
+            const float b0 = __shfl(beta, src0), b1 = __shfl(beta, src1);
+            beta = c + fminf(b0, b1);
+            if (mine) alpha[t * 16 + s] = a + beta;
+            c = cn;
+            a = an;
+        }
+    }
+    wave_lds_fence();
+    // ---- delta, one lane per symbol; the lane's 16 reads start at its own state so that the rows of a wave spread over the banks
+    for (int t = lane; t < T; t += 64) {
+        float mo = __builtin_inff(), me = __builtin_inff();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int s = (i + lane) & 15;
+            const float v = alpha[t * 16 + s];
+            if (s & 1) mo = fminf(mo, v);
+            else me = fminf(me, v);
+        }
+        const float d = mo - me;
+        sh.delta[t] = d;
+        if (delta_out) delta_out[r * delta_ld + t] = d;
+    }
+    wave_lds_fence();
+    // ---- byte reliabilities and their order
+    {
+        float rho = __builtin_inff();
+        if (lane < n) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) rho = fminf(rho, fabsf(sh.delta[8 * lane + i]));
+        }
+        sh.rho[lane] = rho;
+        sh.order[lane] = (unsigned char)(lane < n ? lane : 0);  // (NaN reliabilities may leave ranks unassigned: still a byte of the word)
+        wave_lds_fence();
+        int rank = 0;
+        for (int i = 0; i < n; ++i) {
+            const float ri = sh.rho[i];
+            rank += (ri < rho || (ri == rho && i < lane)) ? 1 : 0;
+        }
+        if (lane < n && rank < m) sh.order[rank] = (unsigned char)lane;
+    }
+    // ---- candidate 0: the hard decoder's codeword
+    int synd[NS + 1];
+    byword_decode_row<NS>(sh, lane, n, nsym, synd, sh.raw);
+    byword_encode_row<NS>(sh, lane, n, nsym);
+    for (int p = lane; p < n; p += 64) sh.cand[p] = sh.row[p];
+    // ---- candidates 1 .. ncand, one per lane: unrank the subset, fill the erasures
+    unsigned char *mine = sh.cand + lane * kCandStride;
+    const bool valid = lane <= ncand;
+    if (lane >= 1 && valid) {
+        int pos[NS], mag[NS];
+        int rem = lane - 1, x = 0;
+#pragma unroll
+        for (int l = 0; l < NS; ++l) {
+            pos[l] = 0;
+            if (l < nsym) {
+                for (;;) {
+                    const int cnt = list_binom(m - 1 - x, nsym - 1 - l);
+                    if (rem < cnt || x >= m - 1) break;
+                    rem -= cnt;
+                    ++x;
+                }
+                pos[l] = sh.order[x];
+                ++x;
+            }
+        }
+        rs_erasure_fill<NS>(&sh.gf, synd, pos, n, nsym, mag);
+        const unsigned int *src = reinterpret_cast<const unsigned int *>(sh.raw);
+        unsigned int *dst = reinterpret_cast<unsigned int *>(mine);
+        for (int w = 0; w < (n + 3) >> 2; ++w) dst[w] = src[w];
+#pragma unroll
+        for (int l = 0; l < NS; ++l)
+            if (l < nsym) mine[pos[l]] ^= (unsigned char)mag[l];
+    }
+    wave_lds_fence();
+    // ---- every candidate's own path through the branch costs
+    float M = __builtin_inff();
+    if (valid) {
+        M = 0.0f;
+        int nxt = mine[0];
+        for (int jb = 0; jb < n; ++jb) {
+            const int cur = nxt;
+            nxt = jb + 1 < n ? mine[jb + 1] : 0;
+            const int w = (cur << 8) | nxt;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int nib = (w >> (12 - i)) & 15;                                   // b[t] b[t+1] b[t+2] b[t+3], b[t] highest
+                const int st = (int)((0xF7B3D591E6A2C480ull >> (4 * nib)) & 15);       // its bits reversed: sum_i 2^i b[t + i]
+                M = M + cost[(8 * jb + i) * 16 + st];
+            }
+        }
+    }
+    // ---- the smallest metric, the lowest index among equals (lane 0's view of the butterfly decides)
+    int best = lane;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float oM = __shfl_xor(M, off);
+        const int ob = __shfl_xor(best, off);
+        if (oM < M || (oM == M && ob < best)) {
+            M = oM;
+            best = ob;
+        }
+    }
+    best = __builtin_amdgcn_readfirstlane(best);
+    if (best > ncand) best = 0;  // (only NaN metrics can leave an unused lane's index here)
+    if (lane == 0 && choice_out) choice_out[r] = best;
+    if (best != 0)
+        for (int p = lane; p < n; p += 64) sh.row[p] = sh.cand[best * kCandStride + p];
+    wave_lds_fence();
+    byword_codec<NS, true>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, 0);
+}
+
+template <int NS>
+__global__ __launch_bounds__(64 * kCoopWaves, 4) void byword_list_step_kernel(
+    const float *__restrict__ rx, int64_t rx_ld, const float *__restrict__ tx, int64_t tx_ld, const float *__restrict__ W1,
+    const float *__restrict__ b1, const float *__restrict__ W2, const float *__restrict__ b2, const float *__restrict__ W3,
+    const float *__restrict__ b3, WeightStrides ws, float *__restrict__ dec, int64_t dec_ld, float *__restrict__ msg,
+    int64_t msg_ld, float *__restrict__ enc, int64_t enc_ld, float *__restrict__ label_word, int64_t lw_ld,
+    int *__restrict__ labels, int64_t lab_ld, int *__restrict__ nerr_out, float *__restrict__ delta_out, int64_t delta_ld,
+    int *__restrict__ choice_out, int T, int nsym, int m, int ncand) {
+    __shared__ ListStepShared<NS> sh;
+    constexpr bool kClosedForm = NS <= 2;
+    const int64_t r = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int k = (T >> 3) - nsym;
+    gf_load(&sh.gf);
+    {
+        const float *txb = tx ? tx + r * tx_ld : nullptr;  // (no transmitted word: a decoder, nothing is counted)
+        for (int p = blockDim.x - 1 - threadIdx.x; p < k; p += blockDim.x)
+            sh.txrow[p] = txb ? (unsigned char)pack_byte(txb + 8 * p) : (unsigned char)0;
+    }
+    float m_unused;
+    float *alpha = nullptr;
+    const int role = coop_detect_block<false, true, true>(rx + r * rx_ld, W1 + r * ws.s[0], b1 + r * ws.s[1], W2 + r * ws.s[2],
+                                                          b2 + r * ws.s[3], W3 + r * ws.s[4], b3 + r * ws.s[5], nullptr, T, &m_unused,
+                                                          [](int, float, bool) {}, sh.surv, sh.fm, &alpha);
+    if (role != kCoopDecided) return;
+    path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
+    if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
+    wave_lds_fence();
+    byword_list_tail<NS>(sh, alpha - ((T + 15) >> 4) * 256, alpha, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld,
+                         nerr_out, delta_out, delta_ld, choice_out, T, nsym, m, ncand);
+}
+
+template <int NS>
+__global__ __launch_bounds__(64) void byword_list_step_va_kernel(
+    const float *__restrict__ rx, int64_t rx_ld, const float *__restrict__ tx, int64_t tx_ld, const float *__restrict__ priors,
+    int64_t Bp, float *__restrict__ dec, int64_t dec_ld, float *__restrict__ msg, int64_t msg_ld, float *__restrict__ enc,
+    int64_t enc_ld, float *__restrict__ label_word, int64_t lw_ld, int *__restrict__ labels, int64_t lab_ld,
+    int *__restrict__ nerr_out, float *__restrict__ delta_out, int64_t delta_ld, int *__restrict__ choice_out, int T, int nsym,
+    int m, int ncand) {
+    __shared__ ListStepShared<NS> sh;
+    extern __shared__ float va_list_img[];  // cost[t][16], then alpha[t][16], 16 * ceil(T / 16) rows each
+    constexpr bool kClosedForm = NS <= 2;
+    const int64_t r = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int k = (T >> 3) - nsym;
+    float *cost = va_list_img, *alpha = va_list_img + ((T + 15) >> 4) * 256;
+    gf_load(&sh.gf);
+    {
+        const float *txb = tx ? tx + r * tx_ld : nullptr;
+        for (int p = lane; p < k; p += 64) sh.txrow[p] = txb ? (unsigned char)pack_byte(txb + 8 * p) : (unsigned char)0;
+    }
+    va16_tile_block_surv<true>(rx + r * rx_ld, priors + (r % Bp) * 16, T, sh.surv, sh.fm, cost, alpha);
+    path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
+    if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
+    wave_lds_fence();
+    byword_list_tail<NS>(sh, cost, alpha, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, delta_out,
+                         delta_ld, choice_out, T, nsym, m, ncand);
 }

@@ -1681,6 +1681,91 @@ int mvn_va_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx,
                           labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
 }
 
+// ---- the block step with the reliability-ordered list decode (byword_step.inc)
+// the list step's own limits, after the step's: T <= 512 (costs and forward metrics stay in LDS), nsym <= m <= T / 8 bytes in the
+// list, C(m, nsym) <= 63 candidates (one wave).  Returns C(m, nsym), or 0 when a limit is broken.
+static int list_step_candidates(int32_t T, int32_t nsym, int32_t m) {
+    if (T > kListMaxT || m < nsym || m > T / 8) return 0;
+    long long c = 1;
+    for (int i = 1; i <= nsym; ++i) {
+        c = c * (m - nsym + i) / i;
+        if (c > 100000) return 0;
+    }
+    return c <= kListMaxCand ? (int)c : 0;
+}
+
+int mvn_vnet_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                  const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                  float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                  float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                  int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                  int64_t delta_ld, int32_t *choice, mvn_stream_t stream) {
+    if (S != 16) return MVN_E_STATES;
+    if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
+    const int ncand = list_step_candidates(T, nsym, list_bytes);
+    if (ncand == 0 || (delta && delta_ld < T)) return MVN_E_DIMS;
+    if (pilot)  // a pilot detects nothing: the existing pilot step
+        return vnet_byword_step(false, rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
+                                label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    const int K = T - 8 * nsym;
+    if (rx_ld < T || (tx && tx_ld < K) || (dec && dec_ld < T) || (msg && msg_ld < K) || (enc && enc_ld < T) ||
+        (label_word && lw_ld < T) || (labels && lab_ld < T))
+        return MVN_E_DIMS;
+    if (R == 0) return MVN_OK;
+    if (!rx || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || (!tx && (nerr || label_word || labels))) return MVN_E_NULL;
+    WeightStrides ws;
+    for (int a = 0; a < 6; ++a) ws.s[a] = w_stride ? (long long)w_stride[a] : 0;
+    const size_t dyn = (size_t)((T + 15) / 16) * 2048;  // costs and forward metrics, 1 KB per 16-symbol tile each
+    hipStream_t st = (hipStream_t)stream;
+#define MVN_LIST_STEP_LAUNCH(NS)                                                                                          \
+    do {                                                                                                                \
+        int e = ensure_dynamic_lds((const void *)byword_list_step_kernel<NS>, (size_t)(kListMaxT / 16 * 2048));           \
+        if (e) return e;                                                                                                \
+        hipLaunchKernelGGL((byword_list_step_kernel<NS>), dim3((unsigned)R), dim3(64 * kCoopWaves), dyn, st, rx, rx_ld,  \
+                           tx, tx_ld, W1, b1, W2, b2, W3, b3, ws, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word,     \
+                           lw_ld, labels, lab_ld, nerr, delta, delta_ld, choice, T, nsym, list_bytes, ncand);           \
+    } while (0)
+    if (nsym <= 2) MVN_LIST_STEP_LAUNCH(2);
+    else MVN_LIST_STEP_LAUNCH(8);
+#undef MVN_LIST_STEP_LAUNCH
+    return (int)hipGetLastError();
+}
+
+int mvn_va_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                int64_t delta_ld, int32_t *choice, mvn_stream_t stream) {
+    if (S != 16) return MVN_E_STATES;
+    if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
+    const int ncand = list_step_candidates(T, nsym, list_bytes);
+    if (ncand == 0 || (delta && delta_ld < T)) return MVN_E_DIMS;
+    if (pilot)
+        return va_byword_step(false, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,
+                              labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    const int K = T - 8 * nsym;
+    if (rx_ld < T || (tx && tx_ld < K) || (dec && dec_ld < T) || (msg && msg_ld < K) || (enc && enc_ld < T) ||
+        (label_word && lw_ld < T) || (labels && lab_ld < T))
+        return MVN_E_DIMS;
+    if (Bp < 1) return MVN_E_PRIORS;
+    if (R == 0) return MVN_OK;
+    if (!rx || !state_priors || (!tx && (nerr || label_word || labels))) return MVN_E_NULL;
+    const size_t dyn = (size_t)((T + 15) / 16) * 2048;
+    hipStream_t st = (hipStream_t)stream;
+#define MVN_LIST_STEP_VA_LAUNCH(NS)                                                                                       \
+    do {                                                                                                                \
+        int e = ensure_dynamic_lds((const void *)byword_list_step_va_kernel<NS>, (size_t)(kListMaxT / 16 * 2048));        \
+        if (e) return e;                                                                                                \
+        hipLaunchKernelGGL((byword_list_step_va_kernel<NS>), dim3((unsigned)R), dim3(64), dyn, st, rx, rx_ld, tx, tx_ld, \
+                           state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld,   \
+                           nerr, delta, delta_ld, choice, T, nsym, list_bytes, ncand);                                  \
+    } while (0)
+    if (nsym <= 2) MVN_LIST_STEP_VA_LAUNCH(2);
+    else MVN_LIST_STEP_VA_LAUNCH(8);
+#undef MVN_LIST_STEP_VA_LAUNCH
+    return (int)hipGetLastError();
+}
+
 void mvn_reload_switches(void) { load_switches(); }
 
 #ifdef MVN_TEST_HOOKS

@@ -185,6 +185,43 @@ __device__ __forceinline__ int rs_forney_correct(const GfTables *gfp, const int 
     return 0;
 }
 
+// Erasure-only Forney for ONE word (the calling lane's): the nsym byte positions pos[0 .. nsym) (distinct, < n) are erased, the
+// other n - nsym bytes are kept, and mag[l] is what must be xor-ed onto byte pos[l] to make the word a codeword (the code is MDS:
+// exactly one such codeword exists).  With X_l = 2^(n - 1 - pos[l]) the magnitudes solve sum_l mag_l X_l^i = synd[i + 1],
+// i = 0 .. nsym - 1; with Lambda(x) = prod_m (x + X_m) and Q_l(x) = Lambda(x) / (x + X_l) = sum_i q_i x^i,
+//     sum_i q_i synd[i + 1] = sum_m mag_m Q_l(X_m) = mag_l Q_l(X_l),
+// so each magnitude is one synthetic division, one dot product and one Horner evaluation.  Everything stays in registers (loops
+// unrolled to NS, guarded by nsym).  Positions that coincide (only possible when the caller ranked NaN reliabilities) give
+// Q_l(X_l) = 0; gf_div's table index stays in range and the result is then unspecified.
+template <int NS>
+__device__ __forceinline__ void rs_erasure_fill(const GfTables *gfp, const int (&synd)[NS + 1], const int (&pos)[NS], int n, int nsym,
+                                                int (&mag)[NS]) {
+    int X[NS], lam[NS + 1];  // lam[d]: coefficient of x^d
+    lam[0] = 1;
+#pragma unroll
+    for (int d = 1; d <= NS; ++d) lam[d] = 0;
+#pragma unroll
+    for (int m = 0; m < NS; ++m) {
+        X[m] = m < nsym ? gf_pow2(gfp, n - 1 - pos[m]) : 0;
+        if (m < nsym) {
+#pragma unroll
+            for (int d = NS; d >= 0; --d) lam[d] = (d > 0 ? lam[d - 1] : 0) ^ gf_mul(gfp, X[m], lam[d]);  // times (x + X_m)
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < NS; ++l) {
+        int q = 0, num = 0, den = 0;
+#pragma unroll
+        for (int d = NS; d >= 1; --d)
+            if (d <= nsym) {
+                q = lam[d] ^ gf_mul(gfp, X[l], q);  // q_{d-1}
+                num ^= gf_mul(gfp, q, synd[d]);
+                den = gf_mul(gfp, den, X[l]) ^ q;
+            }
+        mag[l] = l < nsym ? gf_div(gfp, num, den) : 0;
+    }
+}
+
 // Everything after the syndromes for ONE codeword (the calling lane's): Berlekamp-Massey, exhaustive root search, Forney, and the
 // correction of the message bytes row[0 .. n - nsym - 1] in place.  synd[0] = 0, synd[i + 1] = msg(2^i); `any` = OR of the
 // syndromes.  Returns the status word of mvn_rs_decode_bits_f32 (0 decoded, 1 too many errors, 2 the reference would raise).

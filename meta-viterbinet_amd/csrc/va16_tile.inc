@@ -76,8 +76,12 @@ __device__ __forceinline__ float va16_tile_block(const float *__restrict__ yb, c
 // the survivor words of the previous tile (surv16_tile_store, from its recorded metrics + costs) take the decisions' place between
 // the phases; afterwards surv_words[0 .. T) hold every step's word and fm[16] the final metric in logical state order (both LDS,
 // written and fenced by the calling wave).  Same recurrence, same NaN rule for non-finite priors.
+// KEEP (the list step, byword_step.inc): the branch costs and the metrics before every step are left in LDS as well, cost_img[t][state]
+// and alpha_img[t][state], 16 * ceil(T / 16) rows each.
+template <bool KEEP = false>
 __device__ __forceinline__ void va16_tile_block_surv(const float *__restrict__ yb, const float *__restrict__ prior_row, int T,
-                                                     unsigned short *surv_words, float *fm) {
+                                                     unsigned short *surv_words, float *fm, float *cost_img = nullptr,
+                                                     float *alpha_img = nullptr) {
     const int lane = threadIdx.x & 63;
     const int j = lane & 15, q = lane >> 4;
     int ulog[4];
@@ -116,6 +120,13 @@ __device__ __forceinline__ void va16_tile_block_surv(const float *__restrict__ y
         else sweep_tile(std::false_type{}, std::false_type{});
 #pragma unroll
         for (int r = 0; r < 4; ++r) pa[r] = mrec[r] + cost[r];
+        if (KEEP) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                cost_img[(tu + row_time + r) * 16 + ulog[r]] = cost[r];
+                alpha_img[(tu + row_time + r) * 16 + ulog[r]] = mrec[r];
+            }
+        }
     }
     surv16_tile_store(pa, ulog, lane, surv_words + (((T - 1) >> 4) << 4));
     if (q == 0) fm[logical_state(j, T & 3)] = m;

@@ -27,14 +27,19 @@ constexpr int kCoopMaxBlocks = 768;   // three rounds of one workgroup per CU; a
 // off the chain, the same sums the steps formed), wave 1 turns them into the tile's survivor words surv_words[16 tile ..]
 // (surv16_tile_store) and, once wave 0 has left the final metric in fm[16] (logical state order), returns kCoopDecided: the words of
 // steps 0 .. T - 1 and fm are then visible to it.
+// KEEP (with SURV; the list step, byword_step.inc): the branch costs stay where phase 1 put them, costs[t][state], and the metrics
+// before every step stay as well: wave 0 hands the recorded metrics over through alpha (its lane layout, 1 KB per tile, the same
+// floats after costs in the dynamic LDS), wave 1 forms a = metric + cost itself (the same add) and rewrites the tile as
+// alpha[t][state].  The caller's dynamic LDS is then 2 KB per tile.
 enum { kCoopIdle = 0, kCoopSwept = 1, kCoopDecided = 2 };
-template <bool WRITE_LOGITS, bool SURV = false, class Sink>
+template <bool WRITE_LOGITS, bool SURV = false, bool KEEP = false, class Sink>
 __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, const float *__restrict__ W1,
                                                  const float *__restrict__ b1, const float *__restrict__ W2,
                                                  const float *__restrict__ b2, const float *__restrict__ W3,
                                                  const float *__restrict__ b3, float *__restrict__ logits_b, int T,
                                                  float *m_out, Sink sink, unsigned short *surv_words = nullptr,
-                                                 float *fm = nullptr) {
+                                                 float *fm = nullptr, float **alpha_out = nullptr) {
+    static_assert(!KEEP || SURV, "the metrics are kept next to the survivors");
     constexpr int S = 16;
     __shared__ int s_swept;  // tiles whose recorded metrics wave 0 has handed over
     __shared__ Vnet16Image img;              // the weights (vnet16_common.inc)
@@ -51,6 +56,8 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
     const float wmax = img.ldsMax[0], bmax = img.ldsMax[1];
 
     const int tiles = (T + 15) >> 4;
+    float *const alpha = costs + tiles * 16 * S;  // (KEEP only)
+    if (KEEP) *alpha_out = alpha;
     float4 *const tbase = &ldsT[wave][0];
     const int sym_time = sym_time_of(j), row_time = row_time_of(q);
     const int cunit = (lane >> 4) & 1;  // this lane's unit chain: symbol (lane & 15), unit 48 + cunit (lanes >= 32 duplicate)
@@ -102,11 +109,11 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
             if (strict) sweep16_tile<false, true, false>(m, cost, mrec, nsteps, 0, q);  // torch.min's NaN rule (vnet16_common.inc)
             else if (nsteps == 16) sweep16_tile<true, false, false>(m, cost, mrec, nsteps, 0, q);
             else sweep16_tile<false, false, false>(m, cost, mrec, nsteps, 0, q);
-            if (SURV) {
+            if (SURV && !KEEP) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mrec[r] += cost[r];
             }
-            reinterpret_cast<float4 *>(costs + tu * S)[lane] = make_float4(mrec[0], mrec[1], mrec[2], mrec[3]);
+            reinterpret_cast<float4 *>((KEEP ? alpha : costs) + tu * S)[lane] = make_float4(mrec[0], mrec[1], mrec[2], mrec[3]);
             __hip_atomic_store(&s_swept, tile + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         *m_out = m;
@@ -121,8 +128,17 @@ __device__ __forceinline__ int coop_detect_block(const float *__restrict__ yb, c
         const int nsteps = T - tu < 16 ? T - tu : 16;
         const int tdec = tu + row_time + j;
         while (__hip_atomic_load(&s_swept, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= tile) __builtin_amdgcn_s_sleep(1);
-        const float4 mr4 = reinterpret_cast<const float4 *>(costs + tu * S)[lane];
+        const float4 mr4 = reinterpret_cast<const float4 *>((KEEP ? alpha : costs) + tu * S)[lane];
         const float mrec[4] = {mr4.x, mr4.y, mr4.z, mr4.w};
+        if (KEEP) {
+            float a[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = mrec[r] + costs[(tu + row_time + r) * S + ulog[r]];
+            surv16_tile_store(a, ulog, lane, surv_words + tu);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) alpha[(tu + row_time + r) * S + ulog[r]] = mrec[r];  // (every lane's read came first)
+            continue;
+        }
         if (SURV) {
             surv16_tile_store(mrec, ulog, lane, surv_words + tu);
             continue;

@@ -14,7 +14,7 @@ import torch.distributed as dist
 
 from . import metrics as _metrics
 from .channel import estimate_channel, transmit
-from .ecc import rs_decode, rs_encode
+from .ecc import list_step_bytes, rs_decode, rs_encode
 from .trellis import calculate_states
 
 
@@ -93,11 +93,19 @@ def _gpu_counter(detected: torch.Tensor, tx: torch.Tensor, rows: Optional[torch.
 DECISIONS = ("running", "path")
 
 
-def _check_decision(decision: str, detector=None) -> None:
+def _check_decision(decision: str, detector=None, by_word: bool = False) -> None:
     """decision: 'running' = the reference's running argmin (quirk Q1, symbol t decided before stage t is absorbed), 'path' = the
-    traced-back maximum-likelihood word (detector.viterbi_path); the LSTM detectors have no trellis to trace back."""
+    traced-back maximum-likelihood word (detector.viterbi_path); the LSTM detectors have no trellis to trace back.
+    'list' (by_word: eval_by_word only) = the path's word, list-decoded in the one-launch block step (ecc.list_decode)."""
+    if decision == "list":
+        if not by_word:
+            raise ValueError("decision='list' exists in the by-word block step only (eval_by_word, eval_by_word_batched); "
+                             "to decode a batch of words call list_decode(detector, rx, n_symbols)")
+        if not hasattr(detector, "viterbi_path"):
+            raise ValueError(f"decision='list' needs a Viterbi / ViterbiNet detector ({type(detector).__name__} has no trellis)")
+        return
     if decision not in DECISIONS:
-        raise ValueError(f"decision must be one of {DECISIONS}, got {decision!r}")
+        raise ValueError(f"decision must be one of {DECISIONS + ('list',) if by_word else DECISIONS}, got {decision!r}")
     if decision == "path" and not hasattr(detector, "viterbi_path"):
         raise ValueError(f"decision='path' needs a Viterbi / ViterbiNet detector ({type(detector).__name__} has no viterbi_path)")
 
@@ -243,7 +251,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
                  meta_subframes: int = 5, meta_style_online_training: bool = False,
                  graphed_meta: bool = True, hip_meta: bool = True, initial_buffer=None, weights_init: str = "last_frame",
                  meta_training_weights=None, draws=None, fused_step: bool = True, observer=None,
-                 decision: str = "running") -> np.ndarray:
+                 decision: str = "running", list_bytes: Optional[int] = None) -> np.ndarray:
     """Sequential per-block online evaluation: counterpart of Trainer.eval_by_word (trainer.py:267-354).  Everything but the
     control flow stays on the GPU:
         for every block k:  detect (B=1)  ->  data block: RS decode, ser, RS re-encode | pilot: encode the known word
@@ -278,14 +286,19 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     decision: 'running' (default) detects like the reference, by the running argmin (quirk Q1); 'path' detects every block by the
     traced-back maximum-likelihood word -- in the one-launch step where it applies (mvn_vnet_byword_step_path_f32 /
     mvn_va_byword_step_path_f32), else by detector.viterbi_path in the separate launches -- and everything downstream (RS
-    decode, ser, the buffered label word, every update branch) runs unchanged on it.  Not for the LSTM detectors (ValueError)."""
+    decode, ser, the buffered label word, every update branch) runs unchanged on it.  Not for the LSTM detectors (ValueError).
+    decision='list': the path's word, decoded by the reliability-ordered list decoder in the same launch
+    (mvn_vnet_byword_step_list_f32 / mvn_va_byword_step_list_f32; list_bytes = how many least reliable bytes the erasure patterns
+    are drawn from, default n_symbols + 2): the message is the candidate the trellis likes best, and the error count, the re-encoded
+    word and the buffered label word follow from it.  It exists in the one-launch step only: ValueError when the step's conditions
+    (_fused_step_applies, fused_step=True) or T <= 512 do not hold."""
     import copy
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
 
     from .lstm import LSTMDetector, LSTMMetaTrainer, LSTMOnlineTrainer, MetaLSTMDetector
 
-    _check_decision(decision, detector)
+    _check_decision(decision, detector, by_word=True)
     lstm_meta = False  # the Meta-LSTM curve: an LSTMDetector meta-learned by an LSTMMetaTrainer (meta_lstm_trainer.py)
     if isinstance(detector, (LSTMDetector, MetaLSTMDetector)):
         if online_meta:
@@ -305,6 +318,10 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     ser_by_word = np.zeros(N)
     K = tx.shape[1]
     fused = fused_step and _fused_step_applies(detector, rx, n_symbols, pass_count)
+    if decision == "list":
+        list_bytes = _list_step_bytes(detector, rx, n_symbols, pass_count, fused_step, list_bytes)
+    elif list_bytes is not None:
+        raise ValueError("list_bytes belongs to decision='list'")
     if not (self_supervised or online_meta or verbose):
         # No update runs between blocks, so nothing on the host depends on a block's ser: the reference's 300 B=1 detector
         # calls are issued one by one like it issues them, but the per-block error counts stay on the device and ONE
@@ -315,7 +332,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
             for count in range(N):
                 if count % subframes_in_frame != 0:
                     _byword_step(detector, rx[count:count + 1], tx[count:count + 1], n_symbols, False, nerr[count:count + 1],
-                                 outputs=False, gamma=gamma, count=count if pass_count else None, decision=decision)
+                                 outputs=False, gamma=gamma, count=count if pass_count else None, decision=decision,
+                                 list_bytes=list_bytes)
             e = nerr.cpu().numpy()
             data = np.arange(N) % subframes_in_frame != 0
             ser_by_word[data] = _metrics.ser_from_errors(e[data], K)  # the reference's value bit for bit (metrics.py:13-16)
@@ -383,7 +401,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
         status_word = None
         if step_labels:  # ONE launch: detect, RS decode, error count, re-encode, the word to buffer and its states
             label_word, label_states = _byword_step(detector, received_word, transmitted_word, n_symbols, pilot, nerr1, labels=True,
-                                                     decision=decision)
+                                                     decision=decision, list_bytes=list_bytes)
             if sync_words is not None:
                 n_err, status_word = sync_words.tolist()
             else:
@@ -393,7 +411,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
                 ser_by_word[count] = ser
         elif fused:  # ONE launch: detect, RS decode, error count, re-encode (pilot: encode the known word)
             detected_word, encoded_word = _byword_step(detector, received_word, transmitted_word, n_symbols, pilot, nerr1,
-                                                       gamma=gamma, count=count if pass_count else None, decision=decision)
+                                                       gamma=gamma, count=count if pass_count else None, decision=decision,
+                                                       list_bytes=list_bytes)
             ser = 0.0 if pilot else float(_metrics.ser_from_errors(int(nerr1.item()), K))  # calculate_error_rates (:301)
             if not pilot:
                 ser_by_word[count] = ser
@@ -515,21 +534,53 @@ def _fused_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: 
     return isinstance(detector, VADetector) and detector.transmission_length == T and (pass_count or detector.val_words == 1)
 
 
+def _list_step_bytes(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, fused_step: bool, list_bytes) -> int:
+    """decision='list' exists in the one-launch block step only: the validated list_bytes, or a ValueError that names the
+    condition that does not hold (there is no other route to fall back to)."""
+    from .detectors import VADetector, VNETDetector
+
+    T = rx.shape[1]
+    m = list_step_bytes(T, n_symbols, list_bytes)
+    if not fused_step:
+        raise ValueError("decision='list' runs in the one-launch block step: fused_step=False has no list decoder")
+    if not rx.is_cuda:
+        raise ValueError("decision='list' needs the received words on an MI355X (ROCm) device")
+    if getattr(detector, "n_states", None) != 16:
+        raise ValueError("decision='list' needs a 16-state detector")
+    if isinstance(detector, VNETDetector):
+        if pass_count:
+            raise ValueError("decision='list': a ViterbiNet detector takes no block number (pass_count=False)")
+        if detector.transmission_lengths["val"] != T:
+            raise ValueError(f"decision='list': the detector's 'val' length {detector.transmission_lengths['val']} is not the word length {T}")
+    elif isinstance(detector, VADetector):
+        if detector.transmission_length != T:
+            raise ValueError(f"decision='list': the detector's transmission_length {detector.transmission_length} is not the word length {T}")
+        if not (pass_count or detector.val_words == 1):
+            raise ValueError("decision='list': a VADetector with several rows of state priors needs pass_count=True")
+    else:
+        raise ValueError(f"decision='list' needs a VNETDetector or a VADetector, not {type(detector).__name__}")
+    assert _fused_step_applies(detector, rx, n_symbols, pass_count)
+    return m
+
+
 def _byword_step(detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, n_symbols: int, pilot: bool,
                  nerr: torch.Tensor, outputs: bool = True, gamma: float = None, count: int = None, labels: bool = False,
-                 decision: str = "running"):
+                 decision: str = "running", list_bytes: int = None):
     """One block of eval_by_word in one launch (trainer.py:292-316): returns (detected_word, encoded_word) [1, T]; the
     block's bit-error count goes to nerr[0] (device int32).  On a pilot the detection is skipped (never used) and
     detected_word is None.  outputs=False: the error count only (no words are stored, the re-encoding is skipped).
     gamma / count: what VADetector.forward takes to find the word's channel (count None: the detector's single table row).
     labels=True (ViterbiNet): returns (label_word [1, T], states int32 [1, T]) instead -- the word the reference pushes into its
     buffer (:322-324: the detected word if it had bit errors, else the re-encoded one) and its trellis states, both chosen and
-    computed by the kernel.  decision='path': the same step on the traced-back word (the *_path_f32 entry points)."""
+    computed by the kernel.  decision='path': the same step on the traced-back word (the *_path_f32 entry points); decision='list':
+    that step with the list decoder (the *_list_f32 entry points, list_bytes least reliable bytes)."""
     from . import _lib
     from .detectors import VADetector
 
     va_name, vnet_name = (("mvn_va_byword_step_path_f32", "mvn_vnet_byword_step_path_f32") if decision == "path" else
+                          ("mvn_va_byword_step_list_f32", "mvn_vnet_byword_step_list_f32") if decision == "list" else
                           ("mvn_va_byword_step_f32", "mvn_vnet_byword_step_f32"))
+    extra = (list_bytes, None, received_word.shape[1], None) if decision == "list" else ()  # (no delta, no choice)
 
     rxw, txw = _lib.f32c(received_word), _lib.f32c(transmitted_word)
     T, K = rxw.shape[1], txw.shape[1]
@@ -542,7 +593,7 @@ def _byword_step(detector, received_word: torch.Tensor, transmitted_word: torch.
         with _lib.on_device(dev):
             rc = getattr(_lib.load(), va_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, _lib.ptr(pri), 1, _lib.ptr(det), T, None, K,
                                                _lib.ptr(enc), T, None, T, None, T, _lib.ptr(nerr), 1, T, n_symbols,
-                                               1 if pilot else 0, 16, _lib.current_stream(dev))
+                                               1 if pilot else 0, 16, *extra, _lib.current_stream(dev))
         _lib.check(rc, va_name)
         return det, enc
     w = detector._params()
@@ -552,13 +603,13 @@ def _byword_step(detector, received_word: torch.Tensor, transmitted_word: torch.
             rc = getattr(_lib.load(), vnet_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
                                                  None, T, None, K, None, T, _lib.ptr(word), T, _lib.ptr(states), T,
                                                  _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
-                                                 _lib.current_stream(dev))
+                                                 *extra, _lib.current_stream(dev))
         _lib.check(rc, vnet_name)
         return word, states
     with _lib.on_device(dev):
         rc = getattr(_lib.load(), vnet_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
                                              _lib.ptr(det), T, None, K, _lib.ptr(enc), T, None, T, None, T,
                                              _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
-                                             _lib.current_stream(dev))
+                                             *extra, _lib.current_stream(dev))
     _lib.check(rc, vnet_name)
     return det, enc

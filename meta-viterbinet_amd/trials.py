@@ -196,7 +196,7 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
                          window_size: int = 1, meta_train_iterations: int = 20, meta_j_num: int = 10, meta_subframes: int = 5,
                          meta_style_online_training: bool = False, train_minibatch_size: int = 32,
                          weights_init: str = "last_frame", meta_training_weights=None, record: Optional[dict] = None,
-                         cohorts: int = 1, initial_buffer=None, decision: str = "running") -> np.ndarray:
+                         cohorts: int = 1, initial_buffer=None, decision: str = "running", list_bytes: Optional[int] = None) -> np.ndarray:
     """R trials of harness.eval_by_word (= Trainer.eval_by_word, trainer.py:267-354) at once, with the reference's switches:
     buffer_empty True / False, weights_init last_frame / random / meta_training, Adam / RMSprop / SGD.
     tx [R, N, K] message bits, rx [R, N, K + 8 n_symbols] received words (trial r = row r, its own SNR / channel / seed);
@@ -227,13 +227,26 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     is not worth hiding behind it.
     decision='path': every block is detected by the traced-back maximum-likelihood word instead of the reference's running argmin
     (harness.eval_by_word(decision='path')): the lock-step block step is mvn_vnet_byword_step_path_f32 for all R trials, the
-    trial-after-trial route passes the keyword on; an LSTM bank raises ValueError."""
+    trial-after-trial route passes the keyword on; an LSTM bank raises ValueError.
+    decision='list': the path's word, list-decoded in the same launch (mvn_vnet_byword_step_list_f32 for all R trials; list_bytes
+    as in harness.eval_by_word, default n_symbols + 2).  It needs the 16-state step and words of at most 512 symbols: ValueError
+    otherwise, there is no other route."""
     from .lstm_trials import LSTMTrialBank
 
-    if decision not in ("running", "path"):
-        raise ValueError(f"decision must be 'running' or 'path', got {decision!r}")
-    if decision == "path" and isinstance(bank, LSTMTrialBank):
-        raise ValueError("decision='path' needs a Viterbi / ViterbiNet detector (an LSTM detector has no trellis to trace back)")
+    if decision not in ("running", "path", "list"):
+        raise ValueError(f"decision must be 'running', 'path' or 'list', got {decision!r}")
+    if decision in ("path", "list") and isinstance(bank, LSTMTrialBank):
+        raise ValueError(f"decision={decision!r} needs a Viterbi / ViterbiNet detector (an LSTM detector has no trellis to trace back)")
+    if decision == "list":
+        from .ecc import list_step_bytes
+
+        list_bytes = list_step_bytes(rx.shape[2], n_symbols, list_bytes)
+        if bank.n_states != 16:
+            raise ValueError("decision='list' needs a 16-state detector")
+        if not rx.is_cuda:
+            raise ValueError("decision='list' needs the received words on an MI355X (ROCm) device")
+    elif list_bytes is not None:
+        raise ValueError("list_bytes belongs to decision='list'")
 
     R, N = rx.shape[0], rx.shape[1]
     if R != bank.R or len(draws) != R or tx.shape[0] != R:
@@ -262,7 +275,8 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
                                          ser_thresh=ser_thresh, online_meta=online_meta, meta_lr=meta_lr, MAML=MAML, window_size=window_size,
                                          meta_train_iterations=meta_train_iterations, meta_j_num=meta_j_num, meta_subframes=meta_subframes,
                                          meta_style_online_training=meta_style_online_training, weights_init=weights_init,
-                                         meta_training_weights=meta_training_weights, decision=decision), train_minibatch_size)
+                                         meta_training_weights=meta_training_weights, decision=decision, list_bytes=list_bytes),
+                                    train_minibatch_size)
     cohorts = max(1, min(int(cohorts), R))
     bounds = [(c * R) // cohorts for c in range(cohorts + 1)]
     gens = []
@@ -272,7 +286,7 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
                                   ser_by_word[lo:hi], rec, self_supervised, self_supervised_iterations, ser_thresh, online_meta,
                                   meta_lr, MAML, window_size, meta_train_iterations, meta_j_num, meta_subframes,
                                   meta_style_online_training, train_minibatch_size, weights_init, meta_training_weights,
-                                  None if initial_buffer is None else [t[lo:hi] for t in initial_buffer], decision))
+                                  None if initial_buffer is None else [t[lo:hi] for t in initial_buffer], decision, list_bytes))
     with _lib.on_device(rx.device):
         waiting = [next(g) for g in gens]  # every cohort has enqueued its first step and says which event ends it
         while gens:
@@ -332,14 +346,15 @@ def _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser
 def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, self_supervised,
                   self_supervised_iterations, ser_thresh, online_meta, meta_lr, MAML, window_size, meta_train_iterations, meta_j_num,
                   meta_subframes, meta_style_online_training, train_minibatch_size, weights_init, meta_training_weights,
-                  initial_buffer=None, decision="running"):
+                  initial_buffer=None, decision="running", list_bytes=None):
     """One group of trials stepping through its blocks: a generator that enqueues a step's GPU work and yields the event the
     host has to wait for before it can decide what the trials do next (eval_by_word_batched drives one or more of these)."""
     if bank.n_states != 16:
         raise NotImplementedError("the batched evaluation runs the 16-state kernels (mvn_vnet_byword_step_f32)")
     _lib.require_gpu_tensor(rx, "rx")
     lib = _lib.load()
-    step_name = "mvn_vnet_byword_step_path_f32" if decision == "path" else "mvn_vnet_byword_step_f32"
+    step_name = {"path": "mvn_vnet_byword_step_path_f32", "list": "mvn_vnet_byword_step_list_f32"}.get(decision, "mvn_vnet_byword_step_f32")
+    step_extra = (list_bytes, None, rx.shape[2], None) if decision == "list" else ()  # (no delta, no choice)
     step_fn = getattr(lib, step_name)
     dev = rx.device
     R, N, T = rx.shape
@@ -411,7 +426,7 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
                      ctypes.c_void_p(tx.data_ptr() + 4 * count * K), N * K, *wp, w_stride,
                      None, T, None, K, None, T, None, T,
                      ctypes.c_void_p(labels.data_ptr() + 4 * (W0 + count) * T), NA * T,
-                     ctypes.c_void_p(sync_dev.data_ptr()), R, T, n_symbols, pilot, S, stream)
+                     ctypes.c_void_p(sync_dev.data_ptr()), R, T, n_symbols, pilot, S, *step_extra, stream)
         _lib.check(rc, step_name)
         sync_host.copy_(sync_dev, non_blocking=True)
         done.record(ts)
