@@ -353,6 +353,17 @@ int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_
  * T a multiple of 8, T <= 1024, T / 8 > nsym.  Decisions, decoded and encoded words are bit-identical to
  * mvn_vnet_decode_f32 + mvn_rs_decode_bits_f32 + mvn_rs_encode_bits_f32.  Returns MVN_E_STATES for S != 16 and MVN_E_DIMS
  * for nsym > 8 (use the separate entry points there).
+ *
+ * The six block steps (this one, mvn_va_byword_step_f32 and their _path_f32 / _list_f32 forms) share one check, in this order:
+ * S != 16 -> MVN_E_STATES; R < 0 or a broken shape limit -> MVN_E_DIMS; (list) a broken list limit or delta_ld < T with delta given
+ * -> MVN_E_DIMS; a leading dimension too small -> MVN_E_DIMS (rx_ld and tx_ld always, those of the outputs when the output is given);
+ * (VA) Bp < 1 -> MVN_E_PRIORS; R = 0 -> MVN_OK before any pointer is looked at; a required pointer NULL -> MVN_E_NULL.
+ * Which pointers may be NULL:
+ *   every output (dec, msg, enc, label_word, labels, nerr, delta, choice) and w_stride: always;
+ *   rx, and for VA state_priors: on a pilot step (pilot != 0: nothing is detected), with every entry point;
+ *   tx: with the list step's data step only (then tx_ld is not looked at), unless nerr, label_word or labels is asked for;
+ *   W1 .. b3: never, not even on a pilot.
+ * A pilot through a _path_f32 or _list_f32 entry point is the pilot step of this one (after the list's own limits were checked).
  */
 int mvn_vnet_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
                              const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,

@@ -15,6 +15,13 @@ _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 
+# the by-word block steps (mvn_{vnet,va}_byword_step[_path|_list]_f32) share their argument list segment by segment
+_STEP_VNET = [_vp, _i64, _vp, _i64] + [_vp] * 6 + [ctypes.POINTER(ctypes.c_int64)]  # rx, rx_ld, tx, tx_ld, W1 .. b3, w_stride
+_STEP_VA = [_vp, _i64, _vp, _i64, _vp, _i64]                                        # rx, rx_ld, tx, tx_ld, state_priors, Bp
+_STEP_OUT = [_vp, _i64] * 5 + [_vp]             # dec, msg, enc, label_word, labels, each with its leading dimension; nerr
+_STEP_SCALARS = [_i64, _i32, _i32, _i32, _i32]  # R, T, nsym, pilot, S
+_STEP_LIST = [_i32, _vp, _i64, _vp]             # list_bytes, delta, delta_ld, choice
+
 # name -> (restype, argtypes); mirrors include/mvn.h one to one
 SIGNATURES = {
     "mvn_version": (ctypes.c_int, []),
@@ -54,18 +61,12 @@ SIGNATURES = {
     "mvn_vnet_maml_train_trials_f32": (ctypes.c_int, [_vp, _i32, _i32, _i32, ctypes.c_float, _i32] + [ctypes.c_float] * 4 +
                                        [_i32, _vp, ctypes.c_size_t, _vp]),
     "mvn_vnet_train_kernel_name": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.c_size_t, ctypes.c_char_p, _i32]),
-    "mvn_vnet_byword_step_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [ctypes.POINTER(ctypes.c_int64)] +
-                                 [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "mvn_va_byword_step_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32, _i32,
-                                              _i32, _i32, _vp]),
-    "mvn_vnet_byword_step_path_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [ctypes.POINTER(ctypes.c_int64)] +
-                                      [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "mvn_va_byword_step_path_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32,
-                                                   _i32, _i32, _i32, _vp]),
-    "mvn_vnet_byword_step_list_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [ctypes.POINTER(ctypes.c_int64)] +
-                                      [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
-    "mvn_va_byword_step_list_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp, _i64] * 4 + [_vp, _i64, _vp, _i64, _i32,
-                                                   _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mvn_vnet_byword_step_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_va_byword_step_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_vnet_byword_step_path_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_va_byword_step_path_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_vnet_byword_step_list_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
+    "mvn_va_byword_step_list_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
     "mvn_reload_switches": (None, []),
     "mvn_isi_awgn_transmit": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, ctypes.c_double, _vp, _i64, _i64,
                                              _i32, _i32, _vp]),
@@ -156,6 +157,34 @@ def current_stream(device):
     import torch
 
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+class BywordStep:
+    """One of the six by-word block steps of include/mvn.h, mvn_{kind}_byword_step[_path|_list]_f32 (kind 'vnet' / 'va', decision
+    'running' / 'path' / 'list'), for words of T symbols with nsym parity bytes (list: list_bytes least reliable bytes): the symbol
+    and the constant part of its argument list are resolved here, once, outside a caller's block loop."""
+    def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None):
+        self.name = "mvn_%s_byword_step%s_f32" % (kind, {"running": "", "path": "_path", "list": "_list"}[decision])
+        self.fn = getattr(load(), self.name)
+        self.no_T, self.no_K = (None, T), (None, T - 8 * nsym)  # an output that is not asked for, with its row's length
+        self.T, self.nsym = T, nsym
+        if (decision == "list") != (list_bytes is not None):
+            raise ValueError("list_bytes belongs to decision='list', and decision='list' needs it")
+        self.list_bytes = list_bytes
+
+    def __call__(self, device, rx, rx_ld, tx, tx_ld, front, out, nerr, R, pilot, delta=None, delta_ld=None, choice=None, stream=None):
+        """One launch on `device` (None: the caller holds the device guard and passes `stream`), checked.  rx / tx / nerr / delta /
+        choice: pointers (ptr(); None = NULL); front: the detector's part of the list, (W1, b1, W2, b2, W3, b3, w_stride) or
+        (state_priors, Bp); out: {"dec" | "msg" | "enc" | "label_word" | "labels": (pointer, leading dimension)}, what is not named is
+        not written."""
+        get, no_T, T = out.get, self.no_T, self.T
+        tail = () if self.list_bytes is None else (self.list_bytes, delta, T if delta_ld is None else delta_ld, choice)
+        with _NO_GUARD if device is None else on_device(device):
+            rc = self.fn(rx, rx_ld, tx, tx_ld, *front, *get("dec", no_T), *get("msg", self.no_K), *get("enc", no_T),
+                         *get("label_word", no_T), *get("labels", no_T), nerr, R, T, self.nsym, 1 if pilot else 0, 16, *tail,
+                         current_stream(device) if stream is None else stream)
+        if rc:
+            check(rc, self.name)
 
 
 class _NoGuard:

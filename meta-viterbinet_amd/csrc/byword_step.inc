@@ -18,6 +18,13 @@
 // look-ups are dependent LDS round trips: the serial parts are what a B = 1 step waits for.
 // gridDim.x = R words, each with ITS OWN weights (word r uses W + r * stride): R independent trials of the evaluation
 // advance one block per launch (harness.eval_by_word_batched); R = 1 is the reference's sequential call pattern.
+//
+// The family is two detectors times three decision rules (StepDecision): six kernels.  They share the codec, byword_list_tail, the
+// detectors and path16_walk as code, and StepOut / ListOut as types: a kernel packs its output parameters where it calls the codec or
+// the list tail.  The structs travel BY VALUE and each kernel keeps its own staging, detection and finish lines and its LDS in the
+// __global__ function: a const reference to the structs, a reference to the LDS object in a shared staging or finish function, or
+// one more forceinline layer around a kernel's lines each change what the compiler emits for it (the traced-back kernels then measure
+// 1-2 % slower).  Share more here only with an unchanged disassembly of all twelve kernels.
 struct WeightStrides {
     long long s[6];  // elements between consecutive words' W1, b1, W2, b2, W3, b3 (0: all words share one set)
 };
@@ -32,6 +39,22 @@ struct StepShared {
     unsigned char row[kRsRow], txrow[kRsRow];
     unsigned char dbits[kCoopMaxT], lwb[kCoopMaxT + 16];
     int s_loc[NS + 4];  // the error locator and its {length, leading zeros}, from the lane that ran Berlekamp-Massey
+};
+
+enum StepDecision { kStepRunning, kStepPath, kStepList };  // what the codec is fed: running-argmin decisions, the traced-back path, its list decode
+// What a step writes for word r, as in mvn_vnet_byword_step_f32, and the list step's own outputs and limits, as in
+// mvn_vnet_byword_step_list_f32 (an output pointer that is NULL: not wanted).  The kernels pack them from their parameters.
+struct StepOut {
+    float *msg; int64_t msg_ld;
+    float *enc; int64_t enc_ld;
+    float *label_word; int64_t lw_ld;
+    int *labels; int64_t lab_ld;
+    int *nerr;
+};
+struct ListOut {
+    float *delta; int64_t delta_ld;
+    int *choice;
+    int m, ncand;  // list_bytes and C(m, nsym)
 };
 
 // The hard decoder of a data step, by ONE wave: np.packbits of sh.dbits into sh.row (and into raw, when given: the word's bytes as
@@ -133,10 +156,7 @@ __device__ __forceinline__ void byword_encode_row(StepShared<NS> &sh, int lane, 
 // sh.txrow the transmitted message as bytes, sh.gf the tables (and sh.gen the generator polynomial when NS > 2); word r's
 // outputs as in mvn_vnet_byword_step_f32.  CHOSEN (the list step, below): sh.row already holds the codeword to report.
 template <int NS, bool CHOSEN = false>
-__device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int lane, float *__restrict__ msg, int64_t msg_ld,
-                                             float *__restrict__ enc, int64_t enc_ld, float *__restrict__ label_word, int64_t lw_ld,
-                                             int *__restrict__ labels, int64_t lab_ld, int *__restrict__ nerr_out, int T, int nsym,
-                                             int pilot) {
+__device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int lane, StepOut out, int T, int nsym, int pilot) {
     unsigned char *row = sh.row, *txrow = sh.txrow, *dbits = sh.dbits, *lwb = sh.lwb;
     const int n = T >> 3, k = n - nsym;
     // ---- one wave (the deciding wave; wave 0 on a pilot): the codec on the word's byte image
@@ -149,21 +169,21 @@ __device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int 
         for (int p = lane; p < k; p += 64) nerr += __popc((unsigned)(row[p] ^ txrow[p]));
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) nerr += __shfl_xor(nerr, off);
-        if (msg) {
-            float *mb = msg + r * msg_ld;
+        if (out.msg) {
+            float *mb = out.msg + r * out.msg_ld;
             for (int e = lane; e < 8 * k; e += 64) mb[e] = (float)((row[e >> 3] >> (7 - (e & 7))) & 1);
         }
     } else {
         for (int p = lane; p < k; p += 64) row[p] = txrow[p];
     }
-    if (lane == 0 && nerr_out) nerr_out[r] = nerr;
-    if (!enc && !label_word && !labels) return;  // (the evaluation without updates reads the error count only)
+    if (lane == 0 && out.nerr) out.nerr[r] = nerr;
+    if (!out.enc && !out.label_word && !out.labels) return;  // (the evaluation without updates reads the error count only)
     wave_lds_fence();
     if (!CHOSEN) byword_encode_row<NS>(sh, lane, n, nsym);  // encode(decoded) / encode(transmitted)
 
     // ---- encoded word, label word (trainer.py:322-324) and its trellis states
     const bool use_detected = nerr > 0;
-    float *eb = enc ? enc + r * enc_ld : nullptr, *lb = label_word ? label_word + r * lw_ld : nullptr;
+    float *eb = out.enc ? out.enc + r * out.enc_ld : nullptr, *lb = out.label_word ? out.label_word + r * out.lw_ld : nullptr;
     for (int t = lane; t < T + kStepMemory; t += 64) {
         int ebit = 0, lbit = 0;
         if (t < T) {
@@ -175,8 +195,8 @@ __device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int 
         lwb[t] = (unsigned char)lbit;  // zero padding by the memory length (channel_dataset.py:71)
     }
     wave_lds_fence();
-    if (labels) {
-        int *lab = labels + r * lab_ld;
+    if (out.labels) {
+        int *lab = out.labels + r * out.lab_ld;
         for (int t = lane; t < T; t += 64) {
             int st = 0;
 #pragma unroll
@@ -226,7 +246,7 @@ __global__ __launch_bounds__(64 * kCoopWaves, 4) void byword_step_kernel(
         if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);  // (after the detector's workgroup barrier: tables complete)
     }
     wave_lds_fence();
-    byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, pilot);
+    byword_codec<NS>(sh, r, lane, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out}, T, nsym, pilot);
 }
 
 // The same block step for the CLASSICAL Viterbi detector at 16 states (the reference's eval_by_word takes any detector,
@@ -260,7 +280,7 @@ __global__ __launch_bounds__(64) void byword_step_va_kernel(
     wave_lds_fence();  // (one wave: its own LDS writes -- tables, bytes, decisions -- are visible to all its lanes)
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
     wave_lds_fence();
-    byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, pilot);
+    byword_codec<NS>(sh, r, lane, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out}, T, nsym, pilot);
 }
 
 // ---- The block step on the TRACED-BACK PATH (mvn_vnet_byword_step_path_f32 / mvn_va_byword_step_path_f32).  The steps above feed
@@ -299,7 +319,7 @@ __global__ __launch_bounds__(64 * kCoopWaves, 4) void byword_path_step_kernel(
     path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
     wave_lds_fence();
-    byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, 0);
+    byword_codec<NS>(sh, r, lane, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out}, T, nsym, 0);
 }
 
 template <int NS>
@@ -322,7 +342,7 @@ __global__ __launch_bounds__(64) void byword_path_step_va_kernel(
     path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
     wave_lds_fence();
-    byword_codec<NS>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, 0);
+    byword_codec<NS>(sh, r, lane, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out}, T, nsym, 0);
 }
 
 // ---- The block step with a RELIABILITY-ORDERED LIST DECODE (mvn_vnet_byword_step_list_f32 / mvn_va_byword_step_list_f32).  The path
@@ -363,14 +383,11 @@ __device__ __forceinline__ int list_binom(int a, int b) {  // C(a, b), every par
 }
 
 // Everything of a list step after the walk, by ONE wave: sh.dbits = dec, cost / alpha = the [t][16] images, sh.gf / sh.gen / sh.txrow
-// as for byword_codec.  ncand = C(m, nsym).
+// as for byword_codec.  lo.ncand = C(lo.m, nsym).
 template <int NS>
 __device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const float *cost, float *alpha, int64_t r, int lane,
-                                                 float *__restrict__ msg, int64_t msg_ld, float *__restrict__ enc, int64_t enc_ld,
-                                                 float *__restrict__ label_word, int64_t lw_ld, int *__restrict__ labels,
-                                                 int64_t lab_ld, int *__restrict__ nerr_out, float *__restrict__ delta_out,
-                                                 int64_t delta_ld, int *__restrict__ choice_out, int T, int nsym, int m, int ncand) {
-    const int n = T >> 3;
+                                                 StepOut out, ListOut lo, int T, int nsym) {
+    const int n = T >> 3, m = lo.m, ncand = lo.ncand;
     // ---- beta, and alpha + beta in place: lanes 0..15, one per state (the other lanes take part in the cross-lane reads only; what
     // they hold is never read)
     {
@@ -405,7 +422,7 @@ __device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const f
         }
         const float d = mo - me;
         sh.delta[t] = d;
-        if (delta_out) delta_out[r * delta_ld + t] = d;
+        if (lo.delta) lo.delta[r * lo.delta_ld + t] = d;
     }
     wave_lds_fence();
     // ---- byte reliabilities and their order
@@ -489,11 +506,11 @@ __device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const f
     }
     best = __builtin_amdgcn_readfirstlane(best);
     if (best > ncand) best = 0;  // (only NaN metrics can leave an unused lane's index here)
-    if (lane == 0 && choice_out) choice_out[r] = best;
+    if (lane == 0 && lo.choice) lo.choice[r] = best;
     if (best != 0)
         for (int p = lane; p < n; p += 64) sh.row[p] = sh.cand[best * kCandStride + p];
     wave_lds_fence();
-    byword_codec<NS, true>(sh, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, T, nsym, 0);
+    byword_codec<NS, true>(sh, r, lane, out, T, nsym, 0);
 }
 
 template <int NS>
@@ -524,8 +541,8 @@ __global__ __launch_bounds__(64 * kCoopWaves, 4) void byword_list_step_kernel(
     path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
     wave_lds_fence();
-    byword_list_tail<NS>(sh, alpha - ((T + 15) >> 4) * 256, alpha, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld,
-                         nerr_out, delta_out, delta_ld, choice_out, T, nsym, m, ncand);
+    byword_list_tail<NS>(sh, alpha - ((T + 15) >> 4) * 256, alpha, r, lane, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out},
+                         {delta_out, delta_ld, choice_out, m, ncand}, T, nsym);
 }
 
 template <int NS>
@@ -551,6 +568,6 @@ __global__ __launch_bounds__(64) void byword_list_step_va_kernel(
     path16_walk(sh.surv, sh.fm, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);
     wave_lds_fence();
-    byword_list_tail<NS>(sh, cost, alpha, r, lane, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out, delta_out,
-                         delta_ld, choice_out, T, nsym, m, ncand);
+    byword_list_tail<NS>(sh, cost, alpha, r, lane, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out},
+                         {delta_out, delta_ld, choice_out, m, ncand}, T, nsym);
 }

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
@@ -1151,6 +1152,115 @@ int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *man
 #include "lstm.inc"
 #include "lstm_train.inc"
 
+// ---- the by-word block steps (byword_step.inc).  What the six entry points share: they only fill this
+enum StepDetector { kStepVnet, kStepVa };
+struct StepCall {
+    const float *rx; int64_t rx_ld;
+    const float *tx; int64_t tx_ld;
+    float *dec; int64_t dec_ld;  // (NULL, like every output: not wanted)
+    int T, nsym;
+    StepOut out;
+    ListOut list;  // (m = list_bytes; ncand = C(m, nsym) is step_check's to fill)
+    const float *W[6];  // ViterbiNet: W1, b1, W2, b2, W3, b3 and the strides between the words' sets (NULL: one set)
+    const int64_t *w_stride;
+    const float *priors;  // VA: Bp rows of state priors
+    int64_t Bp;
+    int64_t R;
+    int32_t pilot, S;
+    hipStream_t stream;
+};
+
+// the list step's own limits, after the step's: T <= 512 (costs and forward metrics stay in LDS), nsym <= m <= T / 8 bytes in the
+// list, C(m, nsym) <= 63 candidates (one wave).  Returns C(m, nsym), or 0 when a limit is broken.
+int list_step_candidates(int32_t T, int32_t nsym, int32_t m) {
+    if (T > kListMaxT || m < nsym || m > T / 8) return 0;
+    long long c = 1;
+    for (int i = 1; i <= nsym; ++i) {
+        c = c * (m - nsym + i) / i;
+        if (c > 100000) return 0;
+    }
+    return c <= kListMaxCand ? (int)c : 0;
+}
+
+// The checks of a step, in the order the codes are documented in: the state count; the shapes; the list's limits; every leading
+// dimension; the rows of priors (VA); nothing to do (R = 0: MVN_OK before any pointer is looked at); the pointers.  A pilot detects
+// nothing, so a pilot of any decision is the running step and is checked as one: it needs tx and neither rx nor the priors (the
+// ViterbiNet weights are required all the same); only a list data step can do without tx, as long as nothing is compared with it.
+// Leaves the list's number of candidates in c.list.ncand.
+int step_check(StepCall &c, StepDecision decision, StepDetector detector) {
+    const StepOut &o = c.out;
+    const int T = c.T, nsym = c.nsym;
+    if (c.S != 16) return MVN_E_STATES;  // the fused step exists for the 16-state detectors
+    if (c.R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
+    if (decision == kStepList) {
+        c.list.ncand = list_step_candidates(T, nsym, c.list.m);
+        if (c.list.ncand == 0 || (c.list.delta && c.list.delta_ld < T)) return MVN_E_DIMS;
+    }
+    const bool tx_optional = decision == kStepList && !c.pilot;
+    const int K = T - 8 * nsym;
+    if (c.rx_ld < T || ((c.tx || !tx_optional) && c.tx_ld < K) || (c.dec && c.dec_ld < T) || (o.msg && o.msg_ld < K) ||
+        (o.enc && o.enc_ld < T) || (o.label_word && o.lw_ld < T) || (o.labels && o.lab_ld < T))
+        return MVN_E_DIMS;
+    if (detector == kStepVa && c.Bp < 1) return MVN_E_PRIORS;
+    if (c.R == 0) return MVN_OK;
+    if (!c.tx && (!tx_optional || o.nerr || o.label_word || o.labels)) return MVN_E_NULL;
+    if (!c.pilot && (!c.rx || (detector == kStepVa && !c.priors))) return MVN_E_NULL;
+    if (detector == kStepVnet)
+        for (const float *w : c.W)
+            if (!w) return MVN_E_NULL;
+    return MVN_OK;
+}
+
+// One launch of a step kernel, R workgroups of `threads`: the NS = 2 instantiation (parity in closed form) when it serves, else NS = 8
+// (the generator polynomial); dyn_max: what the kernel's dynamic LDS may grow to (0: it takes none).  args: the kernel's, in order.
+template <class... P, class Args>
+int step_launch(void (*k2)(P...), void (*k8)(P...), const StepCall &c, unsigned threads, size_t dyn, size_t dyn_max,
+                const Args &args) {
+    void (*kernel)(P...) = c.nsym <= 2 ? k2 : k8;
+    if (dyn_max)
+        if (int e = ensure_dynamic_lds((const void *)kernel, dyn_max)) return e;
+    std::apply([&](auto... a) { hipLaunchKernelGGL(kernel, dim3((unsigned)c.R), dim3(threads), dyn, c.stream, a...); }, args);
+    return (int)hipGetLastError();
+}
+
+int step_run(StepCall c, StepDecision decision, StepDetector detector) {
+    const int e = step_check(c, decision, detector);
+    if (e != MVN_OK || c.R == 0) return e;
+    if (c.pilot) decision = kStepRunning;  // (the path and list kernels are data steps)
+    const StepOut &o = c.out;
+    const ListOut &l = c.list;
+    const auto words = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld);
+    const auto outs = std::make_tuple(c.dec, c.dec_ld, o.msg, o.msg_ld, o.enc, o.enc_ld, o.label_word, o.lw_ld, o.labels, o.lab_ld,
+                                      o.nerr);
+    const auto running = std::make_tuple(c.T, c.nsym, c.pilot);
+    const auto path = std::make_tuple(c.T, c.nsym);
+    const auto list = std::make_tuple(l.delta, l.delta_ld, l.choice, c.T, c.nsym, l.m, l.ncand);
+    // dynamic LDS per 16-symbol tile: 1 KB of costs (ViterbiNet), for the list 1 KB of forward metrics more
+    const size_t tiles = (size_t)((c.T + 15) / 16), list_max = (size_t)(kListMaxT / 16 * 2048);
+    if (detector == kStepVa) {
+        const auto head = std::tuple_cat(words, std::make_tuple(c.priors, c.Bp), outs);
+        if (decision == kStepRunning)
+            return step_launch(byword_step_va_kernel<2>, byword_step_va_kernel<8>, c, 64, 0, 0, std::tuple_cat(head, running));
+        if (decision == kStepPath)
+            return step_launch(byword_path_step_va_kernel<2>, byword_path_step_va_kernel<8>, c, 64, 0, 0, std::tuple_cat(head, path));
+        return step_launch(byword_list_step_va_kernel<2>, byword_list_step_va_kernel<8>, c, 64, tiles * 2048, list_max,
+                           std::tuple_cat(head, list));
+    }
+    WeightStrides ws;
+    for (int a = 0; a < 6; ++a) ws.s[a] = c.w_stride ? (long long)c.w_stride[a] : 0;
+    const auto head = std::tuple_cat(words, std::make_tuple(c.W[0], c.W[1], c.W[2], c.W[3], c.W[4], c.W[5], ws), outs);
+    const unsigned threads = 64 * kCoopWaves;
+    const size_t coop_max = (size_t)(kCoopMaxT / 16 * 1024);
+    if (decision == kStepRunning)
+        return step_launch(byword_step_kernel<2>, byword_step_kernel<8>, c, threads, c.pilot ? 0 : tiles * 1024, coop_max,
+                           std::tuple_cat(head, running));
+    if (decision == kStepPath)
+        return step_launch(byword_path_step_kernel<2>, byword_path_step_kernel<8>, c, threads, tiles * 1024, coop_max,
+                           std::tuple_cat(head, path));
+    return step_launch(byword_list_step_kernel<2>, byword_list_step_kernel<8>, c, threads, tiles * 2048, list_max,
+                       std::tuple_cat(head, list));
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1569,59 +1679,24 @@ int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_
     return MVN_OK;
 }
 
-// both decision rules of the ViterbiNet block step: path = the traced-back word (data steps only; a pilot detects nothing)
-static int vnet_byword_step(bool path, const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
-                            const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
-                            float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
-                            float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
-                            int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
-    if (S != 16) return MVN_E_STATES;  // the fused step exists for the 16-state detector
-    if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
-    const int K = T - 8 * nsym;
-    if (rx_ld < T || tx_ld < K || (dec && dec_ld < T) || (msg && msg_ld < K) || (enc && enc_ld < T) ||
-        (label_word && lw_ld < T) || (labels && lab_ld < T))
-        return MVN_E_DIMS;
-    if (R == 0) return MVN_OK;
-    if (!tx || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || (!pilot && !rx)) return MVN_E_NULL;
-    WeightStrides ws;
-    for (int a = 0; a < 6; ++a) ws.s[a] = w_stride ? (long long)w_stride[a] : 0;
-    const size_t dyn = pilot ? 0 : (size_t)((T + 15) / 16) * 1024;
-    hipStream_t st = (hipStream_t)stream;
-#define MVN_STEP_LAUNCH(NS)                                                                                              \
-    do {                                                                                                                \
-        int e = ensure_dynamic_lds((const void *)byword_step_kernel<NS>, (size_t)(kCoopMaxT / 16 * 1024));               \
-        if (e) return e;                                                                                                \
-        hipLaunchKernelGGL((byword_step_kernel<NS>), dim3((unsigned)R), dim3(64 * kCoopWaves), dyn, st, rx, rx_ld, tx,    \
-                           tx_ld, W1, b1, W2, b2, W3, b3, ws, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,   \
-                           labels, lab_ld, nerr, T, nsym, pilot);                                                       \
-    } while (0)
-#define MVN_PATH_STEP_LAUNCH(NS)                                                                                         \
-    do {                                                                                                                \
-        int e = ensure_dynamic_lds((const void *)byword_path_step_kernel<NS>, (size_t)(kCoopMaxT / 16 * 1024));          \
-        if (e) return e;                                                                                                \
-        hipLaunchKernelGGL((byword_path_step_kernel<NS>), dim3((unsigned)R), dim3(64 * kCoopWaves), dyn, st, rx, rx_ld,  \
-                           tx, tx_ld, W1, b1, W2, b2, W3, b3, ws, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word,     \
-                           lw_ld, labels, lab_ld, nerr, T, nsym);                                                       \
-    } while (0)
-    if (path && !pilot) {
-        if (nsym <= 2) MVN_PATH_STEP_LAUNCH(2);
-        else MVN_PATH_STEP_LAUNCH(8);
-    } else {
-        if (nsym <= 2) MVN_STEP_LAUNCH(2);
-        else MVN_STEP_LAUNCH(8);
-    }
-#undef MVN_PATH_STEP_LAUNCH
-#undef MVN_STEP_LAUNCH
-    return (int)hipGetLastError();
-}
-
+// ---- the by-word block steps (byword_step.inc): StepCall, step_check and step_run above
 int mvn_vnet_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
                              const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
                              float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
                              float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                              int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
-    return vnet_byword_step(false, rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
-                            label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                     {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
+                    kStepRunning, kStepVnet);
+}
+
+int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                           float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                           float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                           int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                     {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                    kStepRunning, kStepVa);
 }
 
 int mvn_vnet_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
@@ -1629,69 +1704,18 @@ int mvn_vnet_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *t
                                   float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
                                   float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                   int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
-    return vnet_byword_step(true, rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
-                            label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
-}
-
-static int va_byword_step(bool path, const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors,
-                          int64_t Bp, float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
-                          float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R, int32_t T,
-                          int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
-    if (S != 16) return MVN_E_STATES;  // the fused step exists for the 16-state detectors
-    if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
-    const int K = T - 8 * nsym;
-    if (rx_ld < T || tx_ld < K || (dec && dec_ld < T) || (msg && msg_ld < K) || (enc && enc_ld < T) ||
-        (label_word && lw_ld < T) || (labels && lab_ld < T))
-        return MVN_E_DIMS;
-    if (Bp < 1) return MVN_E_PRIORS;
-    if (R == 0) return MVN_OK;
-    if (!tx || (!pilot && (!rx || !state_priors))) return MVN_E_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    if (path && !pilot) {
-        if (nsym <= 2)
-            hipLaunchKernelGGL((byword_path_step_va_kernel<2>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors,
-                               Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym);
-        else
-            hipLaunchKernelGGL((byword_path_step_va_kernel<8>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors,
-                               Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym);
-        return (int)hipGetLastError();
-    }
-    if (nsym <= 2)
-        hipLaunchKernelGGL((byword_step_va_kernel<2>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec,
-                           dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym, pilot);
-    else
-        hipLaunchKernelGGL((byword_step_va_kernel<8>), dim3((unsigned)R), dim3(64), 0, st, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec,
-                           dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr, T, nsym, pilot);
-    return (int)hipGetLastError();
-}
-
-int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
-                           float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld, float *label_word,
-                           int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R, int32_t T, int32_t nsym,
-                           int32_t pilot, int32_t S, mvn_stream_t stream) {
-    return va_byword_step(false, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,
-                          labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                     {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
+                    kStepPath, kStepVnet);
 }
 
 int mvn_va_byword_step_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
                                 float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
                                 float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                 int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
-    return va_byword_step(true, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,
-                          labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
-}
-
-// ---- the block step with the reliability-ordered list decode (byword_step.inc)
-// the list step's own limits, after the step's: T <= 512 (costs and forward metrics stay in LDS), nsym <= m <= T / 8 bytes in the
-// list, C(m, nsym) <= 63 candidates (one wave).  Returns C(m, nsym), or 0 when a limit is broken.
-static int list_step_candidates(int32_t T, int32_t nsym, int32_t m) {
-    if (T > kListMaxT || m < nsym || m > T / 8) return 0;
-    long long c = 1;
-    for (int i = 1; i <= nsym; ++i) {
-        c = c * (m - nsym + i) / i;
-        if (c > 100000) return 0;
-    }
-    return c <= kListMaxCand ? (int)c : 0;
+    return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                     {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                    kStepPath, kStepVa);
 }
 
 int mvn_vnet_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
@@ -1700,35 +1724,9 @@ int mvn_vnet_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *t
                                   float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                   int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
                                   int64_t delta_ld, int32_t *choice, mvn_stream_t stream) {
-    if (S != 16) return MVN_E_STATES;
-    if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
-    const int ncand = list_step_candidates(T, nsym, list_bytes);
-    if (ncand == 0 || (delta && delta_ld < T)) return MVN_E_DIMS;
-    if (pilot)  // a pilot detects nothing: the existing pilot step
-        return vnet_byword_step(false, rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
-                                label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
-    const int K = T - 8 * nsym;
-    if (rx_ld < T || (tx && tx_ld < K) || (dec && dec_ld < T) || (msg && msg_ld < K) || (enc && enc_ld < T) ||
-        (label_word && lw_ld < T) || (labels && lab_ld < T))
-        return MVN_E_DIMS;
-    if (R == 0) return MVN_OK;
-    if (!rx || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || (!tx && (nerr || label_word || labels))) return MVN_E_NULL;
-    WeightStrides ws;
-    for (int a = 0; a < 6; ++a) ws.s[a] = w_stride ? (long long)w_stride[a] : 0;
-    const size_t dyn = (size_t)((T + 15) / 16) * 2048;  // costs and forward metrics, 1 KB per 16-symbol tile each
-    hipStream_t st = (hipStream_t)stream;
-#define MVN_LIST_STEP_LAUNCH(NS)                                                                                          \
-    do {                                                                                                                \
-        int e = ensure_dynamic_lds((const void *)byword_list_step_kernel<NS>, (size_t)(kListMaxT / 16 * 2048));           \
-        if (e) return e;                                                                                                \
-        hipLaunchKernelGGL((byword_list_step_kernel<NS>), dim3((unsigned)R), dim3(64 * kCoopWaves), dyn, st, rx, rx_ld,  \
-                           tx, tx_ld, W1, b1, W2, b2, W3, b3, ws, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word,     \
-                           lw_ld, labels, lab_ld, nerr, delta, delta_ld, choice, T, nsym, list_bytes, ncand);           \
-    } while (0)
-    if (nsym <= 2) MVN_LIST_STEP_LAUNCH(2);
-    else MVN_LIST_STEP_LAUNCH(8);
-#undef MVN_LIST_STEP_LAUNCH
-    return (int)hipGetLastError();
+    return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {delta, delta_ld, choice, list_bytes, 0},
+                     {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
+                    kStepList, kStepVnet);
 }
 
 int mvn_va_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
@@ -1736,34 +1734,9 @@ int mvn_va_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx,
                                 float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                 int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
                                 int64_t delta_ld, int32_t *choice, mvn_stream_t stream) {
-    if (S != 16) return MVN_E_STATES;
-    if (R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
-    const int ncand = list_step_candidates(T, nsym, list_bytes);
-    if (ncand == 0 || (delta && delta_ld < T)) return MVN_E_DIMS;
-    if (pilot)
-        return va_byword_step(false, rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,
-                              labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
-    const int K = T - 8 * nsym;
-    if (rx_ld < T || (tx && tx_ld < K) || (dec && dec_ld < T) || (msg && msg_ld < K) || (enc && enc_ld < T) ||
-        (label_word && lw_ld < T) || (labels && lab_ld < T))
-        return MVN_E_DIMS;
-    if (Bp < 1) return MVN_E_PRIORS;
-    if (R == 0) return MVN_OK;
-    if (!rx || !state_priors || (!tx && (nerr || label_word || labels))) return MVN_E_NULL;
-    const size_t dyn = (size_t)((T + 15) / 16) * 2048;
-    hipStream_t st = (hipStream_t)stream;
-#define MVN_LIST_STEP_VA_LAUNCH(NS)                                                                                       \
-    do {                                                                                                                \
-        int e = ensure_dynamic_lds((const void *)byword_list_step_va_kernel<NS>, (size_t)(kListMaxT / 16 * 2048));        \
-        if (e) return e;                                                                                                \
-        hipLaunchKernelGGL((byword_list_step_va_kernel<NS>), dim3((unsigned)R), dim3(64), dyn, st, rx, rx_ld, tx, tx_ld, \
-                           state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld,   \
-                           nerr, delta, delta_ld, choice, T, nsym, list_bytes, ncand);                                  \
-    } while (0)
-    if (nsym <= 2) MVN_LIST_STEP_VA_LAUNCH(2);
-    else MVN_LIST_STEP_VA_LAUNCH(8);
-#undef MVN_LIST_STEP_VA_LAUNCH
-    return (int)hipGetLastError();
+    return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {delta, delta_ld, choice, list_bytes, 0},
+                     {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                    kStepList, kStepVa);
 }
 
 void mvn_reload_switches(void) { load_switches(); }

@@ -105,24 +105,19 @@ def list_decode(detector, rx: torch.Tensor, n_symbols: int, list_bytes=None, ret
     msg = torch.empty((B, K), dtype=torch.float32, device=dev)
     choice = torch.empty(B, dtype=torch.int32, device=dev)
     delta = torch.empty((B, T), dtype=torch.float32, device=dev) if return_delta else None
-    tail = (None, T, _lib.ptr(msg), K, None, T, None, T, None, T, None, B, T, n_symbols, 0, 16, m, _lib.ptr(delta), T, _lib.ptr(choice),
-            _lib.current_stream(dev))
-    with _lib.on_device(dev):
-        if isinstance(detector, VADetector):
-            if detector.transmission_length != T:
-                raise ValueError(f"the detector's transmission_length {detector.transmission_length} is not the word length {T}")
-            pri = detector._priors_table(y, gamma, "val", count)
-            if B % pri.shape[0] != 0:
-                raise ValueError(f"{B} words do not divide into the detector's {pri.shape[0]} rows of state priors")
-            name = "mvn_va_byword_step_list_f32"
-            rc = getattr(_lib.load(), name)(_lib.ptr(y), y.stride(0), None, K, _lib.ptr(pri), pri.shape[0], *tail)
-        else:
-            if detector.transmission_lengths["val"] != T:
-                raise ValueError(f"the detector's 'val' length {detector.transmission_lengths['val']} is not the word length {T}")
-            name = "mvn_vnet_byword_step_list_f32"
-            rc = getattr(_lib.load(), name)(_lib.ptr(y), y.stride(0), None, K, *[_lib.ptr(_lib.f32c(p)) for p in detector._params()],
-                                            None, *tail)
-    _lib.check(rc, name)
+    if isinstance(detector, VADetector):
+        if detector.transmission_length != T:
+            raise ValueError(f"the detector's transmission_length {detector.transmission_length} is not the word length {T}")
+        pri = detector._priors_table(y, gamma, "val", count)
+        if B % pri.shape[0] != 0:
+            raise ValueError(f"{B} words do not divide into the detector's {pri.shape[0]} rows of state priors")
+        kind, front = "va", (_lib.ptr(pri), pri.shape[0])
+    else:
+        if detector.transmission_lengths["val"] != T:
+            raise ValueError(f"the detector's 'val' length {detector.transmission_lengths['val']} is not the word length {T}")
+        kind, front = "vnet", (*[_lib.ptr(_lib.f32c(p)) for p in detector._params()], None)
+    _lib.BywordStep(kind, "list", T, n_symbols, m)(dev, _lib.ptr(y), y.stride(0), None, K, front, {"msg": (_lib.ptr(msg), K)}, None, B,
+                                                   False, delta=_lib.ptr(delta), choice=_lib.ptr(choice))
     return (msg, choice, delta) if return_delta else (msg, choice)
 
 

@@ -322,6 +322,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
         list_bytes = _list_step_bytes(detector, rx, n_symbols, pass_count, fused_step, list_bytes)
     elif list_bytes is not None:
         raise ValueError("list_bytes belongs to decision='list'")
+    step = _block_step(detector, rx.shape[1], n_symbols, decision, list_bytes) if fused else None
     if not (self_supervised or online_meta or verbose):
         # No update runs between blocks, so nothing on the host depends on a block's ser: the reference's 300 B=1 detector
         # calls are issued one by one like it issues them, but the per-block error counts stay on the device and ONE
@@ -331,9 +332,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
             nerr = torch.zeros(N, dtype=torch.int32, device=rx.device)
             for count in range(N):
                 if count % subframes_in_frame != 0:
-                    _byword_step(detector, rx[count:count + 1], tx[count:count + 1], n_symbols, False, nerr[count:count + 1],
-                                 outputs=False, gamma=gamma, count=count if pass_count else None, decision=decision,
-                                 list_bytes=list_bytes)
+                    _byword_step(step, detector, rx[count:count + 1], tx[count:count + 1], False, nerr[count:count + 1],
+                                 outputs=False, gamma=gamma, count=count if pass_count else None)
             e = nerr.cpu().numpy()
             data = np.arange(N) % subframes_in_frame != 0
             ser_by_word[data] = _metrics.ser_from_errors(e[data], K)  # the reference's value bit for bit (metrics.py:13-16)
@@ -400,8 +400,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
         seen = {"count": count, "meta": None, "trained": False, "batch_idx": None} if observer is not None else None
         status_word = None
         if step_labels:  # ONE launch: detect, RS decode, error count, re-encode, the word to buffer and its states
-            label_word, label_states = _byword_step(detector, received_word, transmitted_word, n_symbols, pilot, nerr1, labels=True,
-                                                     decision=decision, list_bytes=list_bytes)
+            label_word, label_states = _byword_step(step, detector, received_word, transmitted_word, pilot, nerr1, labels=True)
             if sync_words is not None:
                 n_err, status_word = sync_words.tolist()
             else:
@@ -410,9 +409,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
             if not pilot:
                 ser_by_word[count] = ser
         elif fused:  # ONE launch: detect, RS decode, error count, re-encode (pilot: encode the known word)
-            detected_word, encoded_word = _byword_step(detector, received_word, transmitted_word, n_symbols, pilot, nerr1,
-                                                       gamma=gamma, count=count if pass_count else None, decision=decision,
-                                                       list_bytes=list_bytes)
+            detected_word, encoded_word = _byword_step(step, detector, received_word, transmitted_word, pilot, nerr1,
+                                                       gamma=gamma, count=count if pass_count else None)
             ser = 0.0 if pilot else float(_metrics.ser_from_errors(int(nerr1.item()), K))  # calculate_error_rates (:301)
             if not pilot:
                 ser_by_word[count] = ser
@@ -563,53 +561,42 @@ def _list_step_bytes(detector, rx: torch.Tensor, n_symbols: int, pass_count: boo
     return m
 
 
-def _byword_step(detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, n_symbols: int, pilot: bool,
-                 nerr: torch.Tensor, outputs: bool = True, gamma: float = None, count: int = None, labels: bool = False,
-                 decision: str = "running", list_bytes: int = None):
-    """One block of eval_by_word in one launch (trainer.py:292-316): returns (detected_word, encoded_word) [1, T]; the
-    block's bit-error count goes to nerr[0] (device int32).  On a pilot the detection is skipped (never used) and
+def _block_step(detector, T: int, n_symbols: int, decision: str, list_bytes):
+    """The detector's one-launch block step for this run (resolved once, before the block loop)."""
+    from . import _lib
+    from .detectors import VADetector
+
+    return _lib.BywordStep("va" if isinstance(detector, VADetector) else "vnet", decision, T, n_symbols, list_bytes)
+
+
+def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, pilot: bool, nerr: torch.Tensor,
+                 outputs: bool = True, gamma: float = None, count: int = None, labels: bool = False):
+    """One block of eval_by_word in one launch (trainer.py:292-316; step: _block_step's): returns (detected_word, encoded_word)
+    [1, T]; the block's bit-error count goes to nerr[0] (device int32).  On a pilot the detection is skipped (never used) and
     detected_word is None.  outputs=False: the error count only (no words are stored, the re-encoding is skipped).
     gamma / count: what VADetector.forward takes to find the word's channel (count None: the detector's single table row).
     labels=True (ViterbiNet): returns (label_word [1, T], states int32 [1, T]) instead -- the word the reference pushes into its
     buffer (:322-324: the detected word if it had bit errors, else the re-encoded one) and its trellis states, both chosen and
-    computed by the kernel.  decision='path': the same step on the traced-back word (the *_path_f32 entry points); decision='list':
-    that step with the list decoder (the *_list_f32 entry points, list_bytes least reliable bytes)."""
+    computed by the kernel.  The step's decision 'path': the same step on the traced-back word (the *_path_f32 entry points);
+    'list': that step with the list decoder (the *_list_f32 entry points, list_bytes least reliable bytes)."""
     from . import _lib
     from .detectors import VADetector
-
-    va_name, vnet_name = (("mvn_va_byword_step_path_f32", "mvn_vnet_byword_step_path_f32") if decision == "path" else
-                          ("mvn_va_byword_step_list_f32", "mvn_vnet_byword_step_list_f32") if decision == "list" else
-                          ("mvn_va_byword_step_f32", "mvn_vnet_byword_step_f32"))
-    extra = (list_bytes, None, received_word.shape[1], None) if decision == "list" else ()  # (no delta, no choice)
 
     rxw, txw = _lib.f32c(received_word), _lib.f32c(transmitted_word)
     T, K = rxw.shape[1], txw.shape[1]
     dev = rxw.device
-    det = None if (pilot or not outputs) else torch.empty((1, T), dtype=torch.float32, device=dev)
-    enc = torch.empty((1, T), dtype=torch.float32, device=dev) if outputs else None
     if isinstance(detector, VADetector):
         pri = detector._priors_table(rxw, gamma, "val", count)  # [W, 16] (one row when count is given)
         assert pri.shape[0] == 1  # (_fused_step_applies sends every other table to the separate launches)
-        with _lib.on_device(dev):
-            rc = getattr(_lib.load(), va_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, _lib.ptr(pri), 1, _lib.ptr(det), T, None, K,
-                                               _lib.ptr(enc), T, None, T, None, T, _lib.ptr(nerr), 1, T, n_symbols,
-                                               1 if pilot else 0, 16, *extra, _lib.current_stream(dev))
-        _lib.check(rc, va_name)
-        return det, enc
-    w = detector._params()
+        front = (_lib.ptr(pri), 1)
+    else:
+        front = (*[_lib.ptr(_lib.f32c(p)) for p in detector._params()], None)
     if labels:
-        word, states = torch.empty((1, T), dtype=torch.float32, device=dev), torch.empty((1, T), dtype=torch.int32, device=dev)
-        with _lib.on_device(dev):
-            rc = getattr(_lib.load(), vnet_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
-                                                 None, T, None, K, None, T, _lib.ptr(word), T, _lib.ptr(states), T,
-                                                 _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
-                                                 *extra, _lib.current_stream(dev))
-        _lib.check(rc, vnet_name)
-        return word, states
-    with _lib.on_device(dev):
-        rc = getattr(_lib.load(), vnet_name)(_lib.ptr(rxw), T, _lib.ptr(txw), K, *[_lib.ptr(_lib.f32c(p)) for p in w], None,
-                                             _lib.ptr(det), T, None, K, _lib.ptr(enc), T, None, T, None, T,
-                                             _lib.ptr(nerr), 1, T, n_symbols, 1 if pilot else 0, 16,
-                                             *extra, _lib.current_stream(dev))
-    _lib.check(rc, vnet_name)
-    return det, enc
+        got = (torch.empty((1, T), dtype=torch.float32, device=dev), torch.empty((1, T), dtype=torch.int32, device=dev))
+        out = {"label_word": (_lib.ptr(got[0]), T), "labels": (_lib.ptr(got[1]), T)}
+    else:
+        got = (None if (pilot or not outputs) else torch.empty((1, T), dtype=torch.float32, device=dev),
+               torch.empty((1, T), dtype=torch.float32, device=dev) if outputs else None)
+        out = {"dec": (_lib.ptr(got[0]), T), "enc": (_lib.ptr(got[1]), T)} if outputs else {}
+    step(dev, _lib.ptr(rxw), T, _lib.ptr(txw), K, front, out, _lib.ptr(nerr), 1, pilot)
+    return got

@@ -353,9 +353,7 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
         raise NotImplementedError("the batched evaluation runs the 16-state kernels (mvn_vnet_byword_step_f32)")
     _lib.require_gpu_tensor(rx, "rx")
     lib = _lib.load()
-    step_name = {"path": "mvn_vnet_byword_step_path_f32", "list": "mvn_vnet_byword_step_list_f32"}.get(decision, "mvn_vnet_byword_step_f32")
-    step_extra = (list_bytes, None, rx.shape[2], None) if decision == "list" else ()  # (no delta, no choice)
-    step_fn = getattr(lib, step_name)
+    step = _lib.BywordStep("vnet", decision, rx.shape[2], n_symbols, list_bytes)
     dev = rx.device
     R, N, T = rx.shape
     K = tx.shape[2]
@@ -412,8 +410,8 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
                   + (bank.off[:6].astype(np.uint64) * np.uint64(4))[None, :])
     sup_off = np.arange(-W, 0)
     table_p = None
-    w_stride = (ctypes.c_int64 * 6)(*([bank.P] * 6))
-    wp = [ctypes.c_void_p(bank.theta.data_ptr() + 4 * int(bank.off[a])) for a in range(6)]
+    front = (*[ctypes.c_void_p(bank.theta.data_ptr() + 4 * int(bank.off[a])) for a in range(6)], (ctypes.c_int64 * 6)(*([bank.P] * 6)))
+    nerr_ptr = ctypes.c_void_p(sync_dev.data_ptr())
     stream = _lib.current_stream(dev)
     ts = torch.cuda.current_stream(dev)
 
@@ -422,12 +420,8 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
     done = torch.cuda.Event()  # (the driver holds the device guard)
     for count in range(N):
         pilot = 1 if count % subframes_in_frame == 0 else 0
-        rc = step_fn(ctypes.c_void_p(rx.data_ptr() + 4 * (W0 + count) * T), NA * T,
-                     ctypes.c_void_p(tx.data_ptr() + 4 * count * K), N * K, *wp, w_stride,
-                     None, T, None, K, None, T, None, T,
-                     ctypes.c_void_p(labels.data_ptr() + 4 * (W0 + count) * T), NA * T,
-                     ctypes.c_void_p(sync_dev.data_ptr()), R, T, n_symbols, pilot, S, *step_extra, stream)
-        _lib.check(rc, step_name)
+        step(None, ctypes.c_void_p(rx.data_ptr() + 4 * (W0 + count) * T), NA * T, ctypes.c_void_p(tx.data_ptr() + 4 * count * K), N * K,
+             front, {"labels": (ctypes.c_void_p(labels.data_ptr() + 4 * (W0 + count) * T), NA * T)}, nerr_ptr, R, pilot, stream=stream)
         sync_host.copy_(sync_dev, non_blocking=True)
         done.record(ts)
         yield done  # the one host sync of the step (the reference has one per trial and block, trainer.py:305)

@@ -69,18 +69,7 @@ def test_argument_validation_needs_no_device(lib):
         assert lib.mvn_vnet_workspace_bytes(10000, 1000, S) == 0
         assert lib.mvn_vnet_workspace_bytes(10, 100, S) == 10 * 100 * S * 4  # a few blocks: mlp_kernel + sweep over logits in scratch
     assert lib.mvn_vnet_workspace_bytes(10000, 100, 256) == 10000 * 100 * 256 * 4  # (fused on request only: MVN_FUSED_IP=1)
-    # the by-word step: 16 states, whole bytes, nsym <= 8, a row stride for every output that is given
-    step = lambda T, nsym, S, R=1, rx_ld=None: lib.mvn_vnet_byword_step_f32(  # noqa: E731
-        None, T if rx_ld is None else rx_ld, None, T, *([None] * 6), None, None, T, None, T, None, T, None, T, None, T, None, R, T,
-        nsym, 0, S, None)
-    assert step(136, 2, 8) == -2 and step(136, 2, 256) == -2
-    assert step(135, 2, 16) == -1 and step(136, 9, 16) == -1 and step(16, 2, 16) == -1 and step(2048, 2, 16) == -1
-    assert step(136, 2, 16, rx_ld=100) == -1
-    assert step(136, 2, 16, R=0) == 0 and step(136, 2, 16) == -4
-    va_step = lambda T, nsym, S, Bp=1, R=1: lib.mvn_va_byword_step_f32(  # noqa: E731
-        None, T, None, T, None, Bp, None, T, None, T, None, T, None, T, None, T, None, R, T, nsym, 0, S, None)
-    assert va_step(136, 2, 8) == -2 and va_step(135, 2, 16) == -1 and va_step(136, 9, 16) == -1 and va_step(136, 2, 16, Bp=0) == -3
-    assert va_step(136, 2, 16, R=0) == 0 and va_step(136, 2, 16) == -4
+    # (the by-word steps: tests/test_step_validation_host.py, one table over the six entry points)
     # trial-batched training: shapes before pointers; no trials = nothing to do; workspace sizes
     assert lib.mvn_vnet_online_train_trials_f32(None, 4, 0, 0, 1e-3, 0.9, 0.999, 1e-8, 16, None, 0, None) == -1
     assert lib.mvn_vnet_online_train_trials_f32(None, 4, 136, 0, 1e-3, 0.9, 0.999, 1e-8, 256, None, 0, None) == -2  # online training: S <= 128

@@ -12,10 +12,10 @@ import torch
 import codec_cases as C
 import meta_viterbinet_amd as mvn
 from meta_viterbinet_amd.trials import TrialBank
+from step_call import SENTINEL, padded as _padded, step
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = {"dec": 7.0, "msg": 7.0, "enc": 7.0, "lw": 7.0, "labels": -1, "nerr": -1}
 ALL = ("dec", "msg", "enc", "lw", "labels", "nerr")
 LD_SHAPES = [(2, 17), (8, 65), (5, 128)]
 REQUESTS = [("nerr",), ("nerr", "labels"), ("msg", "nerr"), ("enc",), ("lw", "labels")]
@@ -32,42 +32,6 @@ def dev():
 def g7w(golden, dev):
     w = C.g7_weights(golden)
     return w, [torch.as_tensor(a).to(dev).contiguous() for a in w]
-
-
-def _padded(a, ld, fill, dev):
-    """Rows of `a` at leading dimension ld on the device, the padding filled with `fill`."""
-    a = np.asarray(a, np.float32)
-    out = np.full((a.shape[0], ld), fill, np.float32)
-    out[:, :a.shape[1]] = a
-    return torch.as_tensor(out).to(dev)
-
-
-def _step(dev, kind, rx, tx, nsym, pilot, want=ALL, ld=None, pri=None, Bp=1, weights=None, w_stride=None):
-    """One launch of mvn_va_byword_step_f32 (kind 'va': pri [Bp, 16] on the device) or mvn_vnet_byword_step_f32 (kind 'vnet': weights =
-    six device pointers, w_stride = None or six strides).  rx [R, T] / tx [R, K] are host arrays; ld: leading dimensions by name (rx, tx
-    and the outputs; default: the row length), the padding of rx filled with NaN and that of tx with 7.  Outputs not in `want` are
-    passed as NULL.  Returns the requested outputs as host arrays INCLUDING their padding, pre-filled with SENTINEL."""
-    R, T = rx.shape
-    K = T - 8 * nsym
-    row = {"rx": T, "tx": K, "dec": T, "msg": K, "enc": T, "lw": T, "labels": T}
-    lds = dict(row, **(ld or {}))
-    rx_d, tx_d = _padded(rx, lds["rx"], np.nan, dev), _padded(tx, lds["tx"], 7.0, dev)
-    out = {}
-    for name in want:
-        shape = (R,) if name == "nerr" else (R, lds[name])
-        out[name] = torch.full(shape, SENTINEL[name], dtype=torch.int32 if name in ("labels", "nerr") else torch.float32, device=dev)
-    p = lambda name: mvn._lib.ptr(out.get(name))  # noqa: E731
-    tail = (p("dec"), lds["dec"], p("msg"), lds["msg"], p("enc"), lds["enc"], p("lw"), lds["lw"], p("labels"), lds["labels"], p("nerr"),
-            R, T, nsym, 1 if pilot else 0, 16, mvn._lib.current_stream(dev))
-    lib = mvn._lib.load()
-    if kind == "va":
-        rc = lib.mvn_va_byword_step_f32(mvn._lib.ptr(rx_d), lds["rx"], mvn._lib.ptr(tx_d), lds["tx"], mvn._lib.ptr(pri), Bp, *tail)
-    else:
-        ws = None if w_stride is None else (ctypes.c_int64 * 6)(*w_stride)
-        rc = lib.mvn_vnet_byword_step_f32(mvn._lib.ptr(rx_d), lds["rx"], mvn._lib.ptr(tx_d), lds["tx"], *weights, ws, *tail)
-    assert rc == 0, rc
-    torch.cuda.synchronize(dev)
-    return {name: t.cpu().numpy() for name, t in out.items()}, row
 
 
 def _explain(b, name, got, want, dec=None):
@@ -106,7 +70,7 @@ def test_va_step_on_chosen_error_patterns(oracle, dev, nsym, n):
     rx = C.clean_channel(b["word"], 0)
     ref = C.reference_step(b["word"], b["msg"], nsym, False)
     for Bp in (1, R):
-        out, row = _step(dev, "va", rx, b["msg"], nsym, False, pri=_priors(dev, Bp), Bp=Bp)
+        out, row = step(dev, "running", "va", rx, b["msg"], nsym, False, pri=_priors(dev, Bp), Bp=Bp)
         if not np.array_equal(out["dec"], b["word"]):  # the precondition: the codec saw the chosen pattern
             pytest.fail("detection: " + _explain(b, "dec", out["dec"], b["word"]))
         _assert_step(b, out, row, ref, b["word"])
@@ -120,7 +84,7 @@ def test_vnet_step_on_chosen_error_patterns(oracle, dev, g7w, nsym, n):
     rx = C.vnet_rx(nsym, n)
     dec = oracle.vnet_decode(rx, g7w[0])
     ref = C.reference_step(dec, b["msg"], nsym, False)
-    out, row = _step(dev, "vnet", rx, b["msg"], nsym, False, weights=[mvn._lib.ptr(t) for t in g7w[1]])
+    out, row = step(dev, "running", "vnet", rx, b["msg"], nsym, False, weights=[mvn._lib.ptr(t) for t in g7w[1]])
     if not np.array_equal(out["dec"], dec):
         pytest.fail("detection: " + _explain(b, "dec", out["dec"], dec, dec))
     _assert_step(b, out, row, ref, dec)
@@ -140,7 +104,7 @@ def test_vnet_step_with_a_weight_set_per_word(oracle, golden, dev, nsym, n):
     dec = np.concatenate([oracle.vnet_decode(rx[r:r + 1], w[r]) for r in range(R)])
     ref = C.reference_step(dec, b["msg"], nsym, False)
     wp = [ctypes.c_void_p(bank.theta.data_ptr() + 4 * int(bank.off[a])) for a in range(6)]
-    out, row = _step(dev, "vnet", rx, b["msg"], nsym, False, weights=wp, w_stride=[bank.P] * 6)
+    out, row = step(dev, "running", "vnet", rx, b["msg"], nsym, False, weights=wp, w_stride=[bank.P] * 6)
     if not np.array_equal(out["dec"], dec):
         pytest.fail("detection: " + _explain(b, "dec", out["dec"], dec, dec))
     _assert_step(b, out, row, ref, dec)
@@ -152,11 +116,29 @@ def test_pilot_step_encodes_the_transmitted_word(oracle, dev, g7w, kind, nsym, n
     """Pilot step: enc = label word = encode(tx) by the oracle, labels its trellis states, nerr 0; dec and msg keep their sentinel."""
     b = C.batch(nsym, n)
     kw = dict(pri=_priors(dev)) if kind == "va" else dict(weights=[mvn._lib.ptr(t) for t in g7w[1]])
-    out, row = _step(dev, kind, C.clean_channel(b["word"], 0), b["msg"], nsym, True, **kw)
+    out, row = step(dev, "running", kind, C.clean_channel(b["word"], 0), b["msg"], nsym, True, **kw)
     ref = C.reference_step(None, b["msg"], nsym, True)
     assert np.array_equal(ref["enc"], oracle.rs_encode_bits(b["msg"], nsym)) and not ref["nerr"].any()
     _assert_step(b, out, row, ref, names=("nerr", "enc", "lw", "labels"))
     assert np.all(out["dec"] == SENTINEL["dec"]) and np.all(out["msg"] == SENTINEL["msg"])
+
+
+@pytest.mark.parametrize("variant", ["running", "path", "list"])
+@pytest.mark.parametrize("kind", ["va", "vnet"])
+@pytest.mark.parametrize("T,nsym", [(16, 1), (40, 3)], ids=["closed_form", "generator"])
+def test_pilot_step_needs_no_received_word(oracle, dev, g7w, kind, variant, T, nsym):
+    """A pilot through every entry point with rx NULL (and, for VA, the priors NULL), R = 2, list_bytes = nsym: enc = label word = the
+    oracle's rs_encode of tx, labels = calculate_states of that word, nerr 0; dec, msg, delta and choice keep their sentinel."""
+    tx = np.random.RandomState(100 * T + nsym).randint(0, 2, (2, T - 8 * nsym)).astype(np.float32)
+    kw = dict(pri=None) if kind == "va" else dict(weights=g7w[1])
+    out, row = step(dev, variant, kind, None, tx, nsym, True, m=nsym, **kw)
+    word = oracle.rs_encode_bits(tx, nsym)
+    assert np.array_equal(out["enc"], word) and np.array_equal(out["lw"], word)
+    assert np.array_equal(out["labels"], oracle.calculate_states(C.L, word).reshape(2, T))
+    assert not out["nerr"].any()
+    for name in set(out) - {"enc", "lw", "labels", "nerr"}:
+        assert np.all(out[name] == SENTINEL[name]), name
+    assert {"dec", "msg"} <= set(out) and (variant != "list" or {"delta", "choice"} <= set(out))
 
 
 # ------------------------------------------------------------------------------------------- leading dimensions, optional outputs
@@ -177,8 +159,8 @@ def test_step_honours_every_leading_dimension(oracle, dev, g7w, kind, nsym, n, p
     b, rx, dec, kw = _kind_inputs(oracle, dev, g7w, kind, nsym, n)
     T, K = 8 * n, 8 * (n - nsym)
     ld = {"rx": T + 3, "tx": K + 5, "dec": T + 1, "msg": K + 2, "enc": T + 7, "lw": T + 4, "labels": T + 6}
-    compact, row = _step(dev, kind, rx, b["msg"], nsym, pilot, **kw)
-    wide, _ = _step(dev, kind, rx, b["msg"], nsym, pilot, ld=ld, **kw)
+    compact, row = step(dev, "running", kind, rx, b["msg"], nsym, pilot, **kw)
+    wide, _ = step(dev, "running", kind, rx, b["msg"], nsym, pilot, ld=ld, **kw)
     for name in ALL:
         got = wide[name] if name == "nerr" else wide[name][:, :row[name]]
         if not np.array_equal(got, compact[name]):
@@ -199,8 +181,8 @@ def test_step_honours_every_leading_dimension(oracle, dev, g7w, kind, nsym, n, p
 def test_step_with_some_outputs_only(oracle, dev, g7w, kind, nsym, n, want):
     """Outputs not requested are NULL; what is requested equals the all-outputs run (and the oracle's step)."""
     b, rx, dec, kw = _kind_inputs(oracle, dev, g7w, kind, nsym, n)
-    full, row = _step(dev, kind, rx, b["msg"], nsym, False, **kw)
-    part, _ = _step(dev, kind, rx, b["msg"], nsym, False, want=want, **kw)
+    full, row = step(dev, "running", kind, rx, b["msg"], nsym, False, **kw)
+    part, _ = step(dev, "running", kind, rx, b["msg"], nsym, False, want=want, **kw)
     assert sorted(part) == sorted(want)
     for name in want:
         if not np.array_equal(part[name], full[name]):

@@ -15,12 +15,11 @@ import list_cases as Lc
 import meta_viterbinet_amd as mvn
 import path_cases as P
 from meta_viterbinet_amd.trials import TrialBank, TrialDraws, eval_by_word_batched
+from step_call import SENTINEL, step
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = {"dec": 7.0, "msg": 7.0, "enc": 7.0, "lw": 7.0, "labels": -1, "nerr": -1, "delta": 7.0, "choice": -1}
 ALL = ("dec", "msg", "enc", "lw", "labels", "nerr", "delta", "choice")
-INT = ("labels", "nerr", "choice")
 # (T, nsym, m): 1.5 tiles; the shortest code; the reference's word with 1, 6 and 28 erasure patterns; nsym = 3 (the generator-polynomial
 # encoder); 8 erasures per pattern; 63 bytes; 64 bytes (the last lane ranks a byte; whole tiles at the LDS maximum)
 SHAPES = [(24, 2, 3), (16, 1, 2), (136, 2, 2), (136, 2, 4), (136, 2, 8), (136, 3, 5), (128, 8, 9), (504, 2, 4), (512, 2, 4)]
@@ -39,51 +38,8 @@ def g7w(golden, dev):
     return w, [torch.as_tensor(a).to(dev).contiguous() for a in w]
 
 
-def _padded(a, ld, fill, dev):
-    a = np.asarray(a, np.float32)
-    out = np.full((a.shape[0], ld), fill, np.float32)
-    out[:, :a.shape[1]] = a
-    return torch.as_tensor(out).to(dev)
-
-
 def _dev_weights(dev, w):
     return [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev).contiguous() for a in w]
-
-
-def _step(dev, kind, rx, tx, nsym, m, pilot=False, want=ALL, ld=None, pri=None, Bp=1, weights=None, w_stride=None, variant="list"):
-    """One launch of mvn_{va,vnet}_byword_step_list_f32 (variant 'path' / 'running': the existing entry points, for the pilot test);
-    rx [R, T] / tx [R, K] host arrays (tx None: NULL); ld: leading dimensions by name (padding of rx NaN, of tx 7).  Outputs not in
-    `want` are NULL.  Returns the requested outputs INCLUDING their padding, pre-filled with SENTINEL, and the row lengths."""
-    R, T = rx.shape
-    K = T - 8 * nsym
-    row = {"rx": T, "tx": K, "dec": T, "msg": K, "enc": T, "lw": T, "labels": T, "delta": T}
-    lds = dict(row, **(ld or {}))
-    rx_d = _padded(rx, lds["rx"], np.nan, dev)
-    tx_d = None if tx is None else _padded(tx, lds["tx"], 7.0, dev)
-    if variant != "list":
-        want = tuple(n for n in want if n not in ("delta", "choice"))
-    out = {}
-    for name in want:
-        shape = (R,) if name in ("nerr", "choice") else (R, lds[name])
-        out[name] = torch.full(shape, SENTINEL[name], dtype=torch.int32 if name in INT else torch.float32, device=dev)
-    p = lambda name: mvn._lib.ptr(out.get(name))  # noqa: E731
-    tail = (p("dec"), lds["dec"], p("msg"), lds["msg"], p("enc"), lds["enc"], p("lw"), lds["lw"], p("labels"), lds["labels"], p("nerr"),
-            R, T, nsym, 1 if pilot else 0, 16)
-    if variant == "list":
-        tail += (m, p("delta"), lds["delta"], p("choice"))
-    tail += (mvn._lib.current_stream(dev),)
-    lib = mvn._lib.load()
-    suffix = {"list": "_list_f32", "path": "_path_f32", "running": "_f32"}[variant]
-    if kind == "va":
-        rc = getattr(lib, "mvn_va_byword_step" + suffix)(mvn._lib.ptr(rx_d), lds["rx"], mvn._lib.ptr(tx_d), lds["tx"], mvn._lib.ptr(pri), Bp,
-                                                         *tail)
-    else:
-        ws = None if w_stride is None else (ctypes.c_int64 * 6)(*w_stride)
-        wp = [a if isinstance(a, ctypes.c_void_p) else mvn._lib.ptr(a) for a in weights]
-        rc = getattr(lib, "mvn_vnet_byword_step" + suffix)(mvn._lib.ptr(rx_d), lds["rx"], mvn._lib.ptr(tx_d), lds["tx"], *wp, ws, *tail)
-    assert rc == 0, rc
-    torch.cuda.synchronize(dev)
-    return {name: t.cpu().numpy() for name, t in out.items()}, row
 
 
 def _assert_step(out, row, exp, names=ALL, what=""):
@@ -138,7 +94,7 @@ def test_list_step_equals_the_referee(oracle, dev, g7w, kind, T, nsym, m, R):
     msg, y, exp = _case(oracle, g7w, kind, T, nsym, m)
     if R == 64 and T >= 128:
         assert (exp["choice"] != 0).any(), "words at 6 dB: some take another candidate than the hard decoder's"
-    out, row = _step(dev, kind, y[:R], msg[:R], nsym, m, **_kw(dev, g7w, kind))
+    out, row = step(dev, "list", kind, y[:R], msg[:R], nsym, m=m, **_kw(dev, g7w, kind))
     _assert_step(out, row, _rows(exp, slice(0, R)), what=f"{kind} T={T} nsym={nsym} m={m} R={R}: ")
 
 
@@ -147,7 +103,7 @@ def test_list_step_equals_the_referee(oracle, dev, g7w, kind, T, nsym, m, R):
 def test_list_step_on_the_host_tests_batches(oracle, dev, g7w, kind, snr):
     """The 6 and 8 dB batches whose conditions test_list_step_host.py asserts (m = 4)."""
     msg, y, exp = _case(oracle, g7w, kind, P.T_HOST, P.NSYM_HOST, 4, snr, P.R_HOST)
-    out, row = _step(dev, kind, y, msg, P.NSYM_HOST, 4, **_kw(dev, g7w, kind))
+    out, row = step(dev, "list", kind, y, msg, P.NSYM_HOST, m=4, **_kw(dev, g7w, kind))
     _assert_step(out, row, _rows(exp, slice(None)), what=f"{kind} {snr} dB: ")
 
 
@@ -160,7 +116,7 @@ def test_vnet_list_step_with_a_weight_set_per_word(oracle, golden, dev):
     exp = [Lc.expected("vnet", y[r:r + 1], msg[r:r + 1], nsym, m, weights=w[r]) for r in range(R)]
     exp = {k: np.concatenate([e[k] for e in exp]) for k in KEYS}
     wp = [ctypes.c_void_p(bank.theta.data_ptr() + 4 * int(bank.off[a])) for a in range(6)]
-    out, row = _step(dev, "vnet", y, msg, nsym, m, weights=wp, w_stride=[bank.P] * 6)
+    out, row = step(dev, "list", "vnet", y, msg, nsym, m=m, weights=wp, w_stride=[bank.P] * 6)
     _assert_step(out, row, exp, what="weight set per word: ")
     assert np.any(Lc.soft(P.costs("vnet", y, w[0]))[2] != exp["delta"])  # the sets do differ
 
@@ -170,7 +126,7 @@ def test_va_list_step_with_a_row_of_priors_per_word(oracle, dev):
     msg, _, y = P.words(T, nsym, R, 6)
     pri = (C.channel()[1] * np.linspace(0.8, 1.2, R, dtype=np.float32)[:, None]).astype(np.float32)
     exp = Lc.expected("va", y, msg, nsym, m, priors=pri)
-    out, row = _step(dev, "va", y, msg, nsym, m, pri=torch.as_tensor(pri).to(dev), Bp=R)
+    out, row = step(dev, "list", "va", y, msg, nsym, m=m, pri=torch.as_tensor(pri).to(dev), Bp=R)
     _assert_step(out, row, _rows(exp, slice(None)), what="priors per word: ")
     assert np.any(Lc.soft(P.costs("va", y))[2] != exp["delta"])
 
@@ -181,7 +137,7 @@ def test_list_step_honours_every_leading_dimension(oracle, dev, g7w, kind, T, ns
     msg, y, exp = _case(oracle, g7w, kind, T, nsym, m)
     K = T - 8 * nsym
     ld = {"rx": T + 3, "tx": K + 5, "dec": T + 1, "msg": K + 2, "enc": T + 7, "lw": T + 4, "labels": T + 6, "delta": T + 9}
-    out, row = _step(dev, kind, y[:5], msg[:5], nsym, m, ld=ld, **_kw(dev, g7w, kind))
+    out, row = step(dev, "list", kind, y[:5], msg[:5], nsym, m=m, ld=ld, **_kw(dev, g7w, kind))
     _assert_step(out, row, _rows(exp, slice(0, 5)), what=f"{kind} T={T} wide rows: ")
 
 
@@ -190,7 +146,7 @@ def test_list_step_honours_every_leading_dimension(oracle, dev, g7w, kind, T, ns
 @pytest.mark.parametrize("kind", P.KINDS)
 def test_list_step_with_some_outputs_only(oracle, dev, g7w, kind, want, with_tx):
     msg, y, exp = _case(oracle, g7w, kind, 136, 2, 4)
-    out, row = _step(dev, kind, y, msg if with_tx else None, 2, 4, want=want, **_kw(dev, g7w, kind))
+    out, row = step(dev, "list", kind, y, msg if with_tx else None, 2, m=4, want=want, **_kw(dev, g7w, kind))
     assert sorted(out) == sorted(want)
     _assert_step(out, row, _rows(exp, slice(None)), names=want, what=f"{kind} outputs {want}: ")
 
@@ -214,8 +170,8 @@ def test_list_step_without_tx_refuses_outputs_that_need_it(dev, g7w, kind):
 @pytest.mark.parametrize("T,nsym,m", [(136, 2, 4), (128, 8, 9)])
 def test_pilot_step_is_the_existing_pilot_step(oracle, dev, g7w, kind, T, nsym, m):
     msg, y, _ = _case(oracle, g7w, kind, T, nsym, m)
-    new, row = _step(dev, kind, y[:5], msg[:5], nsym, m, pilot=True, **_kw(dev, g7w, kind))
-    old, _ = _step(dev, kind, y[:5], msg[:5], nsym, m, pilot=True, variant="running", **_kw(dev, g7w, kind))
+    new, row = step(dev, "list", kind, y[:5], msg[:5], nsym, m=m, pilot=True, **_kw(dev, g7w, kind))
+    old, _ = step(dev, "running", kind, y[:5], msg[:5], nsym, pilot=True, **_kw(dev, g7w, kind))
     for name in old:
         assert np.array_equal(new[name], old[name]), name
     ref = C.reference_step(None, msg[:5], nsym, True)
@@ -242,7 +198,7 @@ def test_list_step_breaks_ties_towards_the_lowest_index(oracle, dev, fast, B, T,
     Ms = np.sort(exp["metrics"], axis=1)
     if B == 70:
         assert (Ms[:, 0] == Ms[:, 1]).any(), "the minimal metric is shared in some word"
-    out, row = _step(dev, "vnet", c["y"], msg, nsym, m, weights=_dev_weights(dev, c["w"]))
+    out, row = step(dev, "list", "vnet", c["y"], msg, nsym, m=m, weights=_dev_weights(dev, c["w"]))
     _assert_step(out, row, _rows(exp, slice(None)), what=f"ties fast={fast} {B}x{T}: ")
 
 

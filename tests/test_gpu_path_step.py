@@ -14,10 +14,10 @@ import exact_nets as X
 import meta_viterbinet_amd as mvn
 import path_cases as P
 from meta_viterbinet_amd.trials import TrialBank, TrialDraws, eval_by_word_batched
+from step_call import SENTINEL, step
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = {"dec": 7.0, "msg": 7.0, "enc": 7.0, "lw": 7.0, "labels": -1, "nerr": -1}
 ALL = ("dec", "msg", "enc", "lw", "labels", "nerr")
 LENGTHS = (24, 128, 136, 520, 1024)  # 1.5 tiles (n = 3); whole tiles; the reference's T; n = 65 (lane-stride wrap); the LDS maximum
 SHAPES = [(T, nsym) for T in LENGTHS for nsym in (1, 2, 8) if nsym < T // 8]
@@ -36,46 +36,8 @@ def g7w(golden, dev):
     return w, [torch.as_tensor(a).to(dev).contiguous() for a in w]
 
 
-def _padded(a, ld, fill, dev):
-    a = np.asarray(a, np.float32)
-    out = np.full((a.shape[0], ld), fill, np.float32)
-    out[:, :a.shape[1]] = a
-    return torch.as_tensor(out).to(dev)
-
-
 def _dev_weights(dev, w):
     return [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev).contiguous() for a in w]
-
-
-def _step(dev, kind, rx, tx, nsym, pilot=False, want=ALL, ld=None, pri=None, Bp=1, weights=None, w_stride=None, path=True):
-    """One launch of mvn_va_byword_step[_path]_f32 (kind 'va': pri [Bp, 16] on the device) or mvn_vnet_byword_step[_path]_f32 (kind
-    'vnet': weights = six device tensors or pointers, w_stride = None or six strides); rx [R, T] / tx [R, K] host arrays; ld: leading
-    dimensions by name (padding of rx NaN, of tx 7).  Outputs not in `want` are NULL.  Returns the requested outputs INCLUDING their
-    padding, pre-filled with SENTINEL, and the row lengths."""
-    R, T = rx.shape
-    K = T - 8 * nsym
-    row = {"rx": T, "tx": K, "dec": T, "msg": K, "enc": T, "lw": T, "labels": T}
-    lds = dict(row, **(ld or {}))
-    rx_d, tx_d = _padded(rx, lds["rx"], np.nan, dev), _padded(tx, lds["tx"], 7.0, dev)
-    out = {}
-    for name in want:
-        shape = (R,) if name == "nerr" else (R, lds[name])
-        out[name] = torch.full(shape, SENTINEL[name], dtype=torch.int32 if name in ("labels", "nerr") else torch.float32, device=dev)
-    p = lambda name: mvn._lib.ptr(out.get(name))  # noqa: E731
-    tail = (p("dec"), lds["dec"], p("msg"), lds["msg"], p("enc"), lds["enc"], p("lw"), lds["lw"], p("labels"), lds["labels"], p("nerr"),
-            R, T, nsym, 1 if pilot else 0, 16, mvn._lib.current_stream(dev))
-    lib = mvn._lib.load()
-    if kind == "va":
-        fn = lib.mvn_va_byword_step_path_f32 if path else lib.mvn_va_byword_step_f32
-        rc = fn(mvn._lib.ptr(rx_d), lds["rx"], mvn._lib.ptr(tx_d), lds["tx"], mvn._lib.ptr(pri), Bp, *tail)
-    else:
-        fn = lib.mvn_vnet_byword_step_path_f32 if path else lib.mvn_vnet_byword_step_f32
-        ws = None if w_stride is None else (ctypes.c_int64 * 6)(*w_stride)
-        wp = [a if isinstance(a, ctypes.c_void_p) else mvn._lib.ptr(a) for a in weights]
-        rc = fn(mvn._lib.ptr(rx_d), lds["rx"], mvn._lib.ptr(tx_d), lds["tx"], *wp, ws, *tail)
-    assert rc == 0, rc
-    torch.cuda.synchronize(dev)
-    return {name: t.cpu().numpy() for name, t in out.items()}, row
 
 
 def _assert_step(out, row, exp, names=ALL, what=""):
@@ -126,7 +88,7 @@ def test_path_step_equals_the_oracle(oracle, dev, g7w, kind, T, nsym, R):
     step on that word.  Words at 8 dB: path and running-argmin words differ in most of them."""
     msg, y, exp = _case(oracle, g7w, kind, T, nsym)
     assert np.any(exp["dec"][:R] != exp["running"][:R]) or R == 1
-    out, row = _step(dev, kind, y[:R], msg[:R], nsym, **_kw(dev, g7w, kind))
+    out, row = step(dev, "path", kind, y[:R], msg[:R], nsym, **_kw(dev, g7w, kind))
     _assert_step(out, row, _rows(exp, slice(0, R)), what=f"{kind} T={T} nsym={nsym} R={R}: ")
 
 
@@ -136,7 +98,7 @@ def test_path_step_on_the_host_tests_batches(oracle, dev, g7w, kind, snr):
     """The exact 6 and 8 dB batches whose floors test_path_step_host.py asserts: the GPU's error counts (and everything else) equal the
     oracle's, so failed words, the 'label word = detected word' branch and decoder status 1 are reached on the GPU too."""
     msg, y, exp = _case(oracle, g7w, kind, P.T_HOST, P.NSYM_HOST, snr, P.R_HOST)
-    out, row = _step(dev, kind, y, msg, P.NSYM_HOST, **_kw(dev, g7w, kind))
+    out, row = step(dev, "path", kind, y, msg, P.NSYM_HOST, **_kw(dev, g7w, kind))
     assert np.array_equal(out["nerr"], exp["nerr"])
     _assert_step(out, row, exp, what=f"{kind} {snr} dB: ")
 
@@ -163,7 +125,7 @@ def test_path_step_equals_the_separate_launches(oracle, dev, g7w, kind):
     lw = torch.where((nerr > 0).reshape(-1, 1), dec, enc)
     lib_route = dict(dec=dec.cpu().numpy(), msg=dmsg.cpu().numpy(), nerr=nerr.cpu().numpy(), enc=enc.cpu().numpy(),
                      label_word=lw.cpu().numpy(), labels=mvn.calculate_states(C.L, lw).reshape(lw.shape).to(torch.int32).cpu().numpy())
-    out, row = _step(dev, kind, y, msg, nsym, **_kw(dev, g7w, kind))
+    out, row = step(dev, "path", kind, y, msg, nsym, **_kw(dev, g7w, kind))
     _assert_step(out, row, lib_route, what=f"{kind} against the separate launches: ")
     assert (lib_route["nerr"] > 0).any() and (lib_route["nerr"] == 0).any()
 
@@ -178,7 +140,7 @@ def test_vnet_path_step_with_a_weight_set_per_word(oracle, golden, dev):
     exp = [P.expected("vnet", y[r:r + 1], msg[r:r + 1], nsym, weights=w[r]) for r in range(R)]
     exp = {k: np.concatenate([e[k] for e in exp]) for k in ("dec", "msg", "nerr", "enc", "label_word", "labels")}
     wp = [ctypes.c_void_p(bank.theta.data_ptr() + 4 * int(bank.off[a])) for a in range(6)]
-    out, row = _step(dev, "vnet", y, msg, nsym, weights=wp, w_stride=[bank.P] * 6)
+    out, row = step(dev, "path", "vnet", y, msg, nsym, weights=wp, w_stride=[bank.P] * 6)
     _assert_step(out, row, exp, what="weight set per word: ")
     shared = P.expected("vnet", y, msg, nsym, weights=w[0])
     assert np.any(shared["dec"] != exp["dec"])  # the sets do decide differently
@@ -191,7 +153,7 @@ def test_va_path_step_with_a_row_of_priors_per_word(oracle, dev):
     msg, _, y = P.words(T, nsym, R, 8)
     pri = (C.channel()[1] * np.linspace(0.5, 1.5, R, dtype=np.float32)[:, None]).astype(np.float32)
     exp = P.expected("va", y, msg, nsym, priors=pri)
-    out, row = _step(dev, "va", y, msg, nsym, pri=torch.as_tensor(pri).to(dev), Bp=R)
+    out, row = step(dev, "path", "va", y, msg, nsym, pri=torch.as_tensor(pri).to(dev), Bp=R)
     _assert_step(out, row, exp, what="priors per word: ")
     assert np.any(P.expected("va", y, msg, nsym)["dec"] != exp["dec"])
 
@@ -202,7 +164,7 @@ def test_path_step_honours_every_leading_dimension(oracle, dev, g7w, kind, T, ns
     msg, y, exp = _case(oracle, g7w, kind, T, nsym)
     K = T - 8 * nsym
     ld = {"rx": T + 3, "tx": K + 5, "dec": T + 1, "msg": K + 2, "enc": T + 7, "lw": T + 4, "labels": T + 6}
-    out, row = _step(dev, kind, y[:5], msg[:5], nsym, ld=ld, **_kw(dev, g7w, kind))
+    out, row = step(dev, "path", kind, y[:5], msg[:5], nsym, ld=ld, **_kw(dev, g7w, kind))
     _assert_step(out, row, _rows(exp, slice(0, 5)), what=f"{kind} T={T} wide rows: ")
 
 
@@ -210,7 +172,7 @@ def test_path_step_honours_every_leading_dimension(oracle, dev, g7w, kind, T, ns
 @pytest.mark.parametrize("kind", P.KINDS)
 def test_path_step_with_some_outputs_only(oracle, dev, g7w, kind, want):
     msg, y, exp = _case(oracle, g7w, kind, 136, 2)
-    out, row = _step(dev, kind, y, msg, 2, want=want, **_kw(dev, g7w, kind))
+    out, row = step(dev, "path", kind, y, msg, 2, want=want, **_kw(dev, g7w, kind))
     assert sorted(out) == sorted(want)
     _assert_step(out, row, exp, names=want, what=f"{kind} outputs {want}: ")
 
@@ -219,8 +181,8 @@ def test_path_step_with_some_outputs_only(oracle, dev, g7w, kind, want):
 @pytest.mark.parametrize("T,nsym", [(136, 2), (128, 8)])
 def test_pilot_step_is_the_existing_pilot_step(oracle, dev, g7w, kind, T, nsym):
     msg, y, _ = _case(oracle, g7w, kind, T, nsym)
-    new, row = _step(dev, kind, y[:5], msg[:5], nsym, pilot=True, **_kw(dev, g7w, kind))
-    old, _ = _step(dev, kind, y[:5], msg[:5], nsym, pilot=True, path=False, **_kw(dev, g7w, kind))
+    new, row = step(dev, "path", kind, y[:5], msg[:5], nsym, pilot=True, **_kw(dev, g7w, kind))
+    old, _ = step(dev, "running", kind, y[:5], msg[:5], nsym, pilot=True, **_kw(dev, g7w, kind))
     for name in ALL:
         assert np.array_equal(new[name], old[name]), name
     ref = C.reference_step(None, msg[:5], nsym, True)
@@ -242,7 +204,7 @@ def test_path_step_breaks_ties_like_torch(oracle, dev, fast, strict, B, T):
     exp = P.expected("vnet", c["y"], msg, nsym, weights=c["w"])
     assert np.array_equal(exp["dec"], c["path"])  # the oracle agrees with the NumPy reference
     wd = _dev_weights(dev, c["w"])
-    out, row = _step(dev, "vnet", c["y"], msg, nsym, weights=wd)
+    out, row = step(dev, "path", "vnet", c["y"], msg, nsym, weights=wd)
     _assert_step(out, row, exp, what=f"ties fast={fast} strict={strict} {B}x{T}: ")
     det = mvn.VNETDetector(16, {"train": T, "val": T}).to(dev)
     with torch.no_grad():
@@ -260,7 +222,7 @@ def test_vnet_path_step_with_partially_nan_costs(oracle, golden, dev):
     w[4][3, 11] = np.nan
     w[4][9, 2] = 1e30
     exp = P.expected("vnet", y, msg, nsym, weights=w)
-    out, row = _step(dev, "vnet", y, msg, nsym, weights=_dev_weights(dev, w))
+    out, row = step(dev, "path", "vnet", y, msg, nsym, weights=_dev_weights(dev, w))
     _assert_step(out, row, exp, what="NaN / 1e30 in W3: ")
 
 
@@ -271,7 +233,7 @@ def test_path_step_with_infinite_samples(oracle, dev, g7w, kind):
     y = y.copy()
     y[1, 40], y[2, 0], y[3, 135], y[4, 77] = np.inf, -np.inf, np.inf, -np.inf
     exp = P.expected(kind, y, msg, nsym, weights=g7w[0])
-    out, row = _step(dev, kind, y, msg, nsym, **_kw(dev, g7w, kind))
+    out, row = step(dev, "path", kind, y, msg, nsym, **_kw(dev, g7w, kind))
     _assert_step(out, row, exp, what=f"{kind} +-inf samples: ")
 
 
@@ -282,7 +244,7 @@ def test_va_path_step_with_a_non_finite_prior(oracle, dev, bad):
     pri = C.channel()[1].copy()
     pri[0, 9] = bad
     exp = P.expected("va", y, msg, nsym, priors=pri)
-    out, row = _step(dev, "va", y, msg, nsym, pri=torch.as_tensor(pri).to(dev))
+    out, row = step(dev, "path", "va", y, msg, nsym, pri=torch.as_tensor(pri).to(dev))
     _assert_step(out, row, exp, what=f"prior {bad}: ")
 
 

@@ -6,7 +6,7 @@ and what of mvn_vnet_byword_step_list_f32 / mvn_va_byword_step_list_f32 and deci
   * On path_cases.words(136, 2, 64, snr), both detectors, m = 4: the list fails on strictly fewer words than the path, on no word the
     path decodes, picks a candidate other than the hard decoder's on at least 5 words, and no two different messages tie in metric.
     tests/test_gpu_list_step.py asserts the GPU's outputs on the same batches equal the referee's, so these carry over.
-  * Argument validation of both entry points on NULL pointers, keyword validation, the ABI version."""
+  * Keyword validation.  (Argument validation of both entry points: tests/test_step_validation_host.py.)"""
 import re
 
 import numpy as np
@@ -85,34 +85,6 @@ def test_no_two_different_messages_tie_in_metric(batches, snr, kind):
             for c in range(a + 1, len(M)):
                 if M[a] == M[c]:
                     assert np.array_equal(cands[a][:K], cands[c][:K]), (r, a, c)
-
-
-def test_list_step_argument_validation():
-    lib = mvn._lib.load()
-
-    def vnet(T, nsym, S, m, R=1, rx_ld=None, delta_ld=None):
-        return lib.mvn_vnet_byword_step_list_f32(None, T if rx_ld is None else rx_ld, None, T, *([None] * 6), None, None, T, None, T, None,
-                                                 T, None, T, None, T, None, R, T, nsym, 0, S, m, None, T if delta_ld is None else delta_ld,
-                                                 None, None)
-
-    def va(T, nsym, S, m, R=1, Bp=1):
-        return lib.mvn_va_byword_step_list_f32(None, T, None, T, None, Bp, None, T, None, T, None, T, None, T, None, T, None, R, T, nsym, 0,
-                                               S, m, None, T, None, None)
-
-    for step in (vnet, va):
-        assert step(136, 2, 8, 4) == -2 and step(136, 2, 256, 4) == -2  # the state count comes first
-        assert step(520, 2, 16, 4) == -1 and step(1024, 2, 16, 4) == -1  # T <= 512
-        assert step(135, 2, 16, 4) == -1 and step(136, 9, 16, 9) == -1 and step(16, 2, 16, 2) == -1
-        assert step(136, 2, 16, 12) == -1  # C(12, 2) = 66 > 63
-        assert step(136, 1, 16, 17) == -4 and step(512, 1, 16, 64) == -1  # C(17, 1) = 17 passes the shapes; C(64, 1) = 64
-        assert step(136, 2, 16, 1) == -1  # m < nsym
-        assert step(136, 2, 16, 18) == -1  # m > T / 8
-        assert step(136, 2, 16, 11) == -4  # C(11, 2) = 55: shapes fine, then the NULL pointers
-        assert step(128, 8, 16, 9) == -4 and step(128, 8, 16, 10) == -4 and step(128, 8, 16, 11) == -1  # 9, 45, 165 candidates
-        assert step(136, 2, 16, 4, R=0) == 0 and step(136, 2, 16, 4) == -4 and step(512, 2, 16, 4) == -4
-    assert vnet(136, 2, 16, 4, rx_ld=100) == -1
-    assert va(136, 2, 16, 4, Bp=0) == -3
-    assert lib.mvn_version() == 6
 
 
 def test_list_step_kernels_resources(resources):  # noqa: F811

@@ -5,8 +5,7 @@ can be tested without a device.
     word in most blocks, leaves fewer failed words, and still leaves some (the 'label word = detected word' branch and decoder
     status 1 are reached).  These are conditions on the inputs, not measurements; tests/test_gpu_path_step.py asserts that the
     GPU's error counts on the same batches equal the oracle's, so the floors carry over.
-  * Argument validation of both entry points with NULL pointers (no device is touched): the table test_abi.py holds for the running
-    step.
+  * (Argument validation of both entry points: tests/test_step_validation_host.py, the table over all six block steps.)
   * The new kernels in the gfx950 code object: they exist, use no scratch, and the ViterbiNet form (which shares the 16-wave
     workgroup's occupancy step) keeps to 128 VGPRs."""
 import re
@@ -75,22 +74,6 @@ def test_tie_cases_hold_a_tied_final_minimum():
             fm = exact_nets.tie_case(16, fast, False, B, T)["fm"]
             n += int(np.sum((fm == fm.min(axis=1, keepdims=True)).sum(axis=1) > 1))
     assert n >= 1, n
-
-
-def test_path_step_argument_validation():
-    lib = mvn._lib.load()
-    step = lambda T, nsym, S, R=1, rx_ld=None: lib.mvn_vnet_byword_step_path_f32(  # noqa: E731
-        None, T if rx_ld is None else rx_ld, None, T, *([None] * 6), None, None, T, None, T, None, T, None, T, None, T, None, R, T,
-        nsym, 0, S, None)
-    assert step(136, 2, 8) == -2 and step(136, 2, 256) == -2
-    assert step(135, 2, 16) == -1 and step(136, 9, 16) == -1 and step(16, 2, 16) == -1 and step(2048, 2, 16) == -1
-    assert step(136, 2, 16, rx_ld=100) == -1
-    assert step(136, 2, 16, R=0) == 0 and step(136, 2, 16) == -4
-    va_step = lambda T, nsym, S, Bp=1, R=1: lib.mvn_va_byword_step_path_f32(  # noqa: E731
-        None, T, None, T, None, Bp, None, T, None, T, None, T, None, T, None, T, None, R, T, nsym, 0, S, None)
-    assert va_step(136, 2, 8) == -2 and va_step(135, 2, 16) == -1 and va_step(136, 9, 16) == -1 and va_step(136, 2, 16, Bp=0) == -3
-    assert va_step(136, 2, 16, R=0) == 0 and va_step(136, 2, 16) == -4
-    assert lib.mvn_version() == 6
 
 
 def test_path_step_kernels_resources(resources):  # noqa: F811
