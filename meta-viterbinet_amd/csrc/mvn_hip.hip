@@ -765,6 +765,18 @@ int launch_vnet16_fused(const float *y, int64_t y_ld, const float *W1, const flo
     if (can_deal) {
         const DealtPlan dp = dplan;
         const unsigned long long nonce = dealt_nonce();  // what a SET hand-off flag holds in this launch: nothing to clear
+#ifndef MVN_DIAG_PHASES  // (the phase counters live in the general form)
+        if (dp.ring == 1 && !logits_out) {  // every wave a ring of its own: the form with the block loop inside
+            if (tx)
+                hipLaunchKernelGGL((vnet16_dealt_ring1_kernel<true>), dim3((unsigned)dp.groups), dim3(64 * kDealtWaves), 0, st, y, y_ld, W1, b1,
+                                   W2, b2, W3, b3, dec, dec_ld, final_metric, (int)B, T, tx, tx_ld, K, row_mask, counters, (float *)workspace,
+                                   dp.groups, dealt_spin_limit(), dealt_skip_ring(), nonce);
+            else
+                hipLaunchKernelGGL((vnet16_dealt_ring1_kernel<false>), dim3((unsigned)dp.groups), dim3(64 * kDealtWaves), 0, st, y, y_ld, W1, b1,
+                                   W2, b2, W3, b3, dec, dec_ld, final_metric, (int)B, T, tx, tx_ld, K, row_mask, counters, (float *)workspace,
+                                   dp.groups, dealt_spin_limit(), dealt_skip_ring(), nonce);
+        } else
+#endif
         if (logits_out)
             hipLaunchKernelGGL((vnet16_dealt_kernel<true>), dim3((unsigned)dp.groups), dim3(64 * kDealtWaves), 0, st, y, y_ld, W1, b1, W2, b2,
                                W3, b3, dec, dec_ld, logits_out, final_metric, (int)B, T, tx, tx_ld, K, row_mask, counters, (float *)workspace,

@@ -449,3 +449,300 @@ __global__ __launch_bounds__(64 * kDealtWaves, SURV ? 5 : 6) void vnet16_dealt_k
     }
 #endif
 }
+
+// ---- The ring-of-one form.  From 8 x groups blocks on every wave is a ring of its own (dealt_plan): it sweeps its own blocks and
+// the path metrics never leave its registers except at the two ends of its range.  What vnet16_dealt_kernel pays per unit for
+// serving rings of 8, 4, 2 and 1 from one loop body -- the next unit's (pos, b, s) with a division where the order jumps, the row
+// pointers, own_prev / one_tile / n0 / n1 / counted, the priority rule's multiplies, the in-group hand-off's code, the partial-tile
+// guards of the sweep and of the stores -- is paid here per BLOCK or not at all.  The range executes as runs of one block's units
+// in the general form's order: [the head: units 0 .. n_head - 1 of the block that continues in the next ring] [whole blocks] [the
+// tail: the last n_tail units of the block the previous ring began].  ONE loop over those runs holds ONE copy of the unit's code --
+// a copy per segment would be three times 6 k-loops, 160 KB of code for the 64 KB instruction cache -- and a run is told from its ends:
+// s1 < U is the head (it publishes its metrics after its last unit), s0 > 0 is the tail (it waits for them before its first sweep).
+// Inside a run every unit but the block's last (s < U - 1) is whole at compile time: both tiles live, no step or store guard, and
+// the next unit's samples are 32 floats on.  The block's last unit is peeled, with the general form's guards and its one-tile
+// k-loop.  The two cross-ring points are the general form's, statement for statement: same workspace line, nonce flags, fences,
+// bounded spin and status word.  The unit's arithmetic is vnet16_common.inc's, called as there: bit-identical decisions.
+// COUNT: mvn_vnet_decode_count_f32 (tx != nullptr); the block's bit errors so far are a scalar register across the run.
+// (No WRITE_LOGITS, no SURV, no MVN_DIAG_PHASES: those launches stay on vnet16_dealt_kernel.)
+// row_time_of / sym_time_of without their selects (which compile to a detour through the exec mask, twice per unit)
+constexpr int dealt_row_time(int q) { return 4 * (q ^ (q >> 1)); }
+constexpr int dealt_sym_time(int i) { return i ^ ((i >> 1) & 4); }
+constexpr bool dealt_times_agree() {
+    for (int i = 0; i < 16; ++i)
+        if (dealt_sym_time(i) != sym_time_of(i) || dealt_row_time(i >> 2) != row_time_of(i >> 2)) return false;
+    return true;
+}
+static_assert(dealt_times_agree(), "the branch-free forms give row_time_of / sym_time_of");
+template <bool COUNT>
+__global__ __launch_bounds__(64 * kDealtWaves, 6) void vnet16_dealt_ring1_kernel(
+    const float *__restrict__ y, int64_t y_ld, const float *__restrict__ W1, const float *__restrict__ b1,
+    const float *__restrict__ W2, const float *__restrict__ b2, const float *__restrict__ W3,
+    const float *__restrict__ b3, float *__restrict__ dec, int64_t dec_ld, float *__restrict__ final_metric, int B, int T,
+    const float *__restrict__ tx, int64_t tx_ld, int K, const unsigned char *__restrict__ row_mask,
+    unsigned long long *__restrict__ counters, float *__restrict__ ws, int n_groups, unsigned spin_limit, int skip_publish_ring,
+    unsigned long long nonce) {
+    constexpr int NT = 2;
+    constexpr int S = 16;
+    __shared__ Vnet16Image img;
+    __shared__ float4 ldsT[kDealtWaves][160];
+    __shared__ Vnet16LaneStates lanes;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const bool odd_w = img.stage(W1, b1, W2, b2, W3, b3);
+    lanes.stage();
+    if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<int *>(ws) = 0;  // the status word
+    const bool strict = __syncthreads_or(odd_w) != 0;  // the prologue's barrier; workgroup-uniform.  No barrier below.
+    const float wmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(img.ldsMax[0])));
+    const float bmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(img.ldsMax[1])));
+
+    // ---- this wave's range of the launch's units (vnet16_dealt_kernel's, at ring = 1) and its runs; all in scalar registers
+    const int ring_g = (int)blockIdx.x * kDealtWaves + wave;
+    const int n_rings = n_groups * kDealtWaves;
+    const int U = (T + kDealtUnit - 1) / kDealtUnit;
+    const long long N = (long long)B * U;
+    const int lo = (int)(N * ring_g / n_rings), hi = (int)(N * (ring_g + 1) / n_rings);
+    const int n = hi - lo;
+    const int n_head = hi % U;
+    const int n_tail = (lo % U) ? U - lo % U : 0;
+    const int has_head = n_head > 0 ? 1 : 0;
+    const int n_blocks = (n - n_head - n_tail) / U;
+    const int n_runs = has_head + n_blocks + (n_tail > 0 ? 1 : 0);
+    const int b_head = hi / U, b_tail = lo / U, b_mid = (lo + n_tail) / U - has_head;  // run r of the whole blocks is block b_mid + r
+    auto run_of = [&](int r, int &rb, int &rs0, int &rs1) {  // run r: units rs0 .. rs1 - 1 of block rb
+        if (r < has_head) rb = b_head, rs0 = 0, rs1 = n_head;
+        else if (r < has_head + n_blocks) rb = b_mid + r, rs0 = 0, rs1 = U;
+        else rb = b_tail, rs0 = U - n_tail, rs1 = U;
+    };
+#if MVN_FN_PRIO
+    // the k-loop's priority by the wave's progress (see vnet16_dealt_kernel), its thresholds as execution numbers
+#if MVN_DEALT_PMODE == 0
+    const int e_p1 = (MVN_DEALT_P1N * n + MVN_DEALT_P1D - 1) / MVN_DEALT_P1D, e_p2 = (MVN_DEALT_P2N * n + MVN_DEALT_P2D - 1) / MVN_DEALT_P2D;
+#elif MVN_DEALT_PMODE == 1
+    const int e_p1 = n - MVN_DEALT_P1N, e_p2 = n - MVN_DEALT_P2N;
+#endif
+#endif
+
+    float4 *const tbase = &ldsT[wave][0];
+    const int q = lane >> 4;
+
+    int b = 0, s0 = 0, s1 = 0;
+    if (n_runs > 0) run_of(0, b, s0, s1);
+    float ynext[NT];
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+        const int t = s0 * kDealtUnit + 16 * u + sym_time_of(lane & 15);
+        ynext[u] = n_runs > 0 ? y[(int64_t)b * y_ld + (t < T ? t : T - 1)] : 0.0f;
+    }
+    int e = 0;  // the unit's number in the wave's order of execution
+
+    for (int r = 0; r < n_runs; ++r) {
+        int bn = b, s0n = s0, s1n = s1;  // the run after this one (after the last: this one again, the prefetch reads what it has read)
+        if (r + 1 < n_runs) run_of(r + 1, bn, s0n, s1n);
+        // per block, once
+        const float *const yrow = y + (int64_t)b * y_ld;
+        const float *const y_after = y + (int64_t)bn * y_ld + s0n * kDealtUnit;  // the first samples of the next run ...
+        const int tl_after = T - 1 - s0n * kDealtUnit;                             // ... and the last valid offset from there
+        float *const decb = dec ? dec + (int64_t)b * dec_ld : nullptr;
+        const bool counted = COUNT && (row_mask == nullptr || row_mask[b] != 0);
+        const float *const txb = counted ? tx + (int64_t)b * tx_ld : nullptr;
+        // what travels along the block, in registers from unit to unit: the path metrics, "the hand-off into this run was
+        // abandoned", the bit errors so far
+        float m = 0.0f;
+        bool bad = false;
+        int carry = 0;
+
+        auto unit = [&](auto whole_c, const int s) {
+            constexpr bool WHOLE = decltype(whole_c)::value;  // both tiles live, not the block's last unit (s + 1 < U)
+            const int t0 = s * kDealtUnit;
+#if MVN_FN_PRIO
+#if MVN_DEALT_PMODE == 2
+            const int c = e % 3;
+            if (c == 0) __builtin_amdgcn_s_setprio(2);
+            else if (c == 1) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+#else
+            if (e < e_p1) __builtin_amdgcn_s_setprio(2);
+            else if (e < e_p2) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+#endif
+#endif
+            int lane_k = lane;
+            asm volatile("" : "+v"(lane_k));
+            const int qk = lane_k >> 4;
+            float *const tbw = reinterpret_cast<float *>(tbase) + 4 * (lane_k & 15) + qk;
+            float4 *const tbr = tbase + (lane_k & 31);
+            const int cunit = lane_k >> 5;
+            float yv[NT];
+            {  // the next unit's samples are requested now: 32 floats on within the run, else the next run's first
+                const bool within = WHOLE && s + 1 < s1;
+                const float *const ynx = within ? yrow + t0 + kDealtUnit : y_after;
+                const int tl = within ? T - 1 - t0 - kDealtUnit : tl_after;
+                const int lt = dealt_sym_time(lane_k & 15);
+#pragma unroll
+                for (int u = 0; u < NT; ++u) {
+                    yv[u] = ynext[u];
+                    const int tn = lt + 16 * u;
+                    ynext[u] = ynx[tn < tl ? tn : tl];
+                }
+            }
+            float ymax = fmaxf(fabsf(yv[0]), fabsf(yv[1]));
+            const bool fast = __all(ymax * wmax + bmax <= kFastSigmoidBound);
+
+            f32x4 acc[NT][3];
+#pragma unroll
+            for (int u = 0; u < NT; ++u)
+#pragma unroll
+                for (int tau = 0; tau < 3; ++tau) acc[u][tau] = f32x4{0.f, 0.f, 0.f, 0.f};
+            float ch[1] = {0.0f};
+            const bool one_tile = !WHOLE && t0 + 16 >= T;  // (the block's last unit may end within its first tile)
+            if (fast && !one_tile) vnet16_kloop<2, true>([](float d) { return sigmoid_from_neg_fast(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
+            else if (!one_tile) vnet16_kloop<2, true>([](float d) { return sigmoid_from_neg(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
+            else if (fast) vnet16_kloop<1, true>([](float d) { return sigmoid_from_neg_fast(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
+            else vnet16_kloop<1, true>([](float d) { return sigmoid_from_neg(d); }, img, yv, lane_k, cunit, tbw, tbr, acc, ch);
+
+            float hl[NT];
+            vnet16_units4849(img, cunit, tbw, tbr, ch, hl);
+
+#if MVN_FN_PRIO
+            __builtin_amdgcn_s_setprio(3);
+#endif
+            // the tile phase in vnet16_dealt_kernel's three passes
+            const int n0 = WHOLE ? 16 : (T - t0 < 16 ? T - t0 : 16);
+            const int n1 = WHOLE ? 16 : (T - t0 - 16 < 0 ? 0 : (T - t0 - 16 < 16 ? T - t0 - 16 : 16));
+            int lane_t = lane;
+            asm volatile("" : "+v"(lane_t));
+            const int jt = lane_t & 15, qt = lane_t >> 4;
+            const int lane4 = 4 * lane;  // (the one lane-derived value that lives across the k-loop within 80 VGPRs: any other, scratch)
+            const int4 ul4 = lanes.ldsLane[lane_t];
+            const int ulog[4] = {ul4.x, ul4.y, ul4.z, ul4.w};
+            const int row_time = dealt_row_time(qt);
+            float cost[NT][4], mrec[NT][4], txv[NT];
+            // ---- pass A
+            {
+                const int row_addr = 4 * (lane_t & 48);
+#pragma unroll
+                for (int u = 0; u < NT; ++u) {
+                    const int tdec = t0 + 16 * u + row_time + jt;
+                    txv[u] = 0.0f;
+                    if (counted && jt < 4 && tdec < K) txv[u] = txb[tdec];
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4) mrec[u][r4] = 0.0f;
+                }
+                float logit[NT][4];
+                vnet16_tile_pass<NT>(img, tbase, lane_t, acc, hl, logit);
+#pragma unroll
+                for (int u = 0; u < NT; ++u)
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4)
+                        cost[u][r4] = -__int_as_float(__builtin_amdgcn_ds_bpermute(row_addr + 4 * ulog[r4], __float_as_int(logit[u][r4])));
+            }
+            // ---- pass B: the tail's first unit takes the block's path metrics from the ring that swept its earlier units
+            if (s0 > 0 && s == s0) {
+                const float *line = ws + (size_t)ring_g * kDealtLineFloats;  // line 1 + (ring_g - 1)
+                const unsigned long long *flag = reinterpret_cast<const unsigned long long *>(line) + 9;
+                unsigned spins = 0;
+                bool ok = true;
+                while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nonce) {
+                    __builtin_amdgcn_s_sleep(32);
+                    if (++spins > spin_limit) {
+                        ok = false;
+                        break;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                m = line[jt];
+                bad = !ok || __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(line)[16]) != 0;
+                if (!ok && lane_t == 0) __hip_atomic_store(reinterpret_cast<int *>(ws), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            // ... the two sweeps ...
+            if constexpr (WHOLE) {
+                if (!strict) {
+                    sweep16_tile<true, false, true>(m, cost[0], mrec[0], 16, lane4, q);
+                    sweep16_tile<true, false, true>(m, cost[1], mrec[1], 16, lane4, q);
+                } else {
+                    sweep16_tile<true, true, true>(m, cost[0], mrec[0], 16, lane4, q);
+                    sweep16_tile<true, true, true>(m, cost[1], mrec[1], 16, lane4, q);
+                }
+            } else if (!strict && n1 == 16) {
+                sweep16_tile<true, false, true>(m, cost[0], mrec[0], 16, lane4, q);
+                sweep16_tile<true, false, true>(m, cost[1], mrec[1], 16, lane4, q);
+            } else if (!strict) {
+                sweep16_tile<false, false, true>(m, cost[0], mrec[0], n0, lane4, q);
+                if (n1 > 0) sweep16_tile<false, false, true>(m, cost[1], mrec[1], n1, lane4, q);
+            } else {
+                sweep16_tile<false, true, true>(m, cost[0], mrec[0], n0, lane4, q);
+                if (n1 > 0) sweep16_tile<false, true, true>(m, cost[1], mrec[1], n1, lane4, q);
+            }
+            // ... and, after the head's last unit, on to the ring that sweeps the block's next unit: one line of the workspace
+            const bool publish = WHOLE && s + 1 == s1 && s1 < U;
+            if (publish) {
+                float *line = ws + (size_t)(1 + ring_g) * kDealtLineFloats;
+                if (ring_g != skip_publish_ring) {
+                    if (lane_t < 16) line[lane_t] = m;
+                    if (lane_t == 16) reinterpret_cast<int *>(line)[16] = bad ? 1 : 0;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the line is visible device-wide before the flag
+                    unsigned long long nv = nonce;  // (opaque: the VGPR copy of the nonce is made here, not kept -- or spilled -- across the unit loop)
+                    asm volatile("" : "+s"(nv));
+                    if (lane_t == 0) __hip_atomic_store(reinterpret_cast<unsigned long long *>(line) + 9, nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+            // ---- pass C: decisions
+            int nerr = 0;
+#pragma unroll
+            for (int u = 0; u < NT; ++u) {
+                const int nsteps = u == 0 ? n0 : n1;
+                const int tdec = t0 + 16 * u + row_time + jt;
+                float mydec = strict ? decide4<true>(mrec[u], ulog, jt) : decide4<false>(mrec[u], ulog, jt);
+                if (bad) mydec = __int_as_float(0x7fc00000);  // an abandoned hand-off: no decision is claimed
+                if (jt < 4 && (WHOLE || row_time + jt < nsteps)) {
+                    if (decb) decb[tdec] = mydec;
+                    if (counted && tdec < K) nerr += ((long long)mydec != (long long)txv[u]) ? 1 : 0;
+                }
+            }
+            // ---- counting launches: the unit's bit errors join the block's carry
+            if constexpr (COUNT) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) nerr += __shfl_xor(nerr, off);
+                int total = __builtin_amdgcn_readfirstlane(nerr) + carry;
+                if (s0 > 0 && s == s0 && !bad) {  // (after an abandoned wait nothing of that line is waited for again)
+                    const int *line = reinterpret_cast<const int *>(ws + (size_t)ring_g * kDealtLineFloats);
+                    unsigned spins = 0;
+                    while (__hip_atomic_load(reinterpret_cast<const unsigned long long *>(line) + 10, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nonce &&
+                           ++spins <= spin_limit)
+                        __builtin_amdgcn_s_sleep(32);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    total += __builtin_amdgcn_readfirstlane(line[17]);
+                }
+                if (publish) {
+                    int *line = reinterpret_cast<int *>(ws + (size_t)(1 + ring_g) * kDealtLineFloats);
+                    if (ring_g != skip_publish_ring) {
+                        if (lane == 0) line[17] = total;
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                        unsigned long long nv = nonce;
+                        asm volatile("" : "+s"(nv));
+                        if (lane == 0) __hip_atomic_store(reinterpret_cast<unsigned long long *>(line) + 10, nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                } else if (WHOLE) {
+                    carry = total;
+                } else if (counted && total != 0 && lane == 0) {  // the block ends here: two global atomics per block in error
+                    atomicAdd(&counters[0], (unsigned long long)total);
+                    atomicAdd(&counters[2], 1ull);
+                }
+            }
+            if (!WHOLE && final_metric) {  // (the lane id is made opaque: nothing lane-derived is hoisted out of the unit loop)
+                int lane_f = lane;
+                asm volatile("" : "+v"(lane_f));
+                if (lane_f < 16) final_metric[(int64_t)b * S + logical_state(lane_f, T & 3)] = m;
+            }
+            ++e;
+        };
+
+        const int s_whole = s1 == U ? U - 1 : s1;  // the run's whole units: s0 .. s_whole - 1
+        for (int s = s0; s < s_whole; ++s) unit(std::true_type{}, s);
+        if (s1 == U) unit(std::false_type{}, U - 1);  // the block's last unit
+        b = bn, s0 = s0n, s1 = s1n;
+    }
+}
