@@ -52,7 +52,7 @@ typedef void *mvn_stream_t; /* hipStream_t */
 
 #define MVN_E_BARRIER (-7)   /* (status words only) a training launch abandoned its device-wide barrier */
 
-#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
+#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32, the list steps, mvn_vnet_byword_step_states_f32, mvn_vnet_byword_step_max_symbols) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
 
 /* ABI version of the loaded library (== MVN_ABI_VERSION). */
 int mvn_version(void);
@@ -370,6 +370,28 @@ int mvn_vnet_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, in
                              float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
                              float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                              int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+
+/*
+ * mvn_vnet_byword_step_f32 for the ViterbiNet detector at S = 4, 8, 32, 64 or 128 states (S = 16 forwards to it, so a caller has
+ * one call for every state count): same arguments, same outputs, one launch, a workgroup per word with the word's own weights
+ * (W3 [S, 50], b3 [S]).  The waves run the word's 16-symbol tiles through mvn_vnet_logits_f32's arithmetic into an on-chip image,
+ * one wavefront then runs mvn_acs_sweep_f32's recurrence on it (branch cost -logit, torch.min / torch.argmin rules, always: there
+ * is no fast path to guard) and carries on with the codec; labels are calculate_states with memory length log2 S.  dec is
+ * bit-identical to mvn_vnet_decode_f32, the rest to mvn_rs_decode_bits_f32 / mvn_rs_encode_bits_f32.
+ * (Added without a bump of MVN_ABI_VERSION, like the path steps.)
+ * The image bounds the word: T <= mvn_vnet_byword_step_max_symbols(S) = min(1024, what a CU's 160 KB of LDS hold next to the W3
+ * image and the codec's state, in whole bytes) -- 1024 at 4, 8, 16 and 32 states, 568 at 64, 256 at 128; 0 for a state count the
+ * step does not serve.
+ * The check, in the order of the steps above: S not in {4, 8, 16, 32, 64, 128} -> MVN_E_STATES; R < 0, T not a multiple of 8,
+ * T / 8 <= nsym, nsym outside 1 .. 8 or T > mvn_vnet_byword_step_max_symbols(S) -> MVN_E_DIMS; a leading dimension too small ->
+ * MVN_E_DIMS; R = 0 -> MVN_OK; a required pointer NULL (the rules above) -> MVN_E_NULL.
+ */
+int32_t mvn_vnet_byword_step_max_symbols(int32_t S);
+int mvn_vnet_byword_step_states_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                    const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                    float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                    float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                    int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
 
 /*
  * The same block step for the classical Viterbi detector (the reference's eval_by_word takes any detector, trainer.py:295):

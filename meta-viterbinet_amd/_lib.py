@@ -62,6 +62,8 @@ SIGNATURES = {
                                        [_i32, _vp, ctypes.c_size_t, _vp]),
     "mvn_vnet_train_kernel_name": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.c_size_t, ctypes.c_char_p, _i32]),
     "mvn_vnet_byword_step_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_vnet_byword_step_max_symbols": (_i32, [_i32]),
+    "mvn_vnet_byword_step_states_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_va_byword_step_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_vnet_byword_step_path_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_va_byword_step_path_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
@@ -159,12 +161,27 @@ def current_stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+STEP_STATES = (4, 8, 32, 64, 128)  # the state counts of mvn_vnet_byword_step_states_f32, next to the 16 of the six steps
+
+
+def step_max_symbols(n_states: int) -> int:
+    """The longest word the ViterbiNet running step serves at n_states (mvn_vnet_byword_step_max_symbols; 0: not served)."""
+    return int(load().mvn_vnet_byword_step_max_symbols(n_states))
+
+
 class BywordStep:
-    """One of the six by-word block steps of include/mvn.h, mvn_{kind}_byword_step[_path|_list]_f32 (kind 'vnet' / 'va', decision
+    """One of the by-word block steps of include/mvn.h, mvn_{kind}_byword_step[_path|_list]_f32 (kind 'vnet' / 'va', decision
     'running' / 'path' / 'list'), for words of T symbols with nsym parity bytes (list: list_bytes least reliable bytes): the symbol
-    and the constant part of its argument list are resolved here, once, outside a caller's block loop."""
-    def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None):
+    and the constant part of its argument list are resolved here, once, outside a caller's block loop.
+    n_states other than 16: mvn_vnet_byword_step_states_f32, which exists for the ViterbiNet running step only (ValueError else)."""
+    def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None, n_states: int = 16):
         self.name = "mvn_%s_byword_step%s_f32" % (kind, {"running": "", "path": "_path", "list": "_list"}[decision])
+        if n_states != 16:
+            if kind != "vnet" or decision != "running":
+                raise ValueError(f"the block step at {n_states} states is the ViterbiNet running step (kind='vnet', decision='running'), "
+                                 f"not kind={kind!r}, decision={decision!r}")
+            self.name = "mvn_vnet_byword_step_states_f32"
+        self.n_states = n_states
         self.fn = getattr(load(), self.name)
         self.no_T, self.no_K = (None, T), (None, T - 8 * nsym)  # an output that is not asked for, with its row's length
         self.T, self.nsym = T, nsym
@@ -181,7 +198,7 @@ class BywordStep:
         tail = () if self.list_bytes is None else (self.list_bytes, delta, T if delta_ld is None else delta_ld, choice)
         with _NO_GUARD if device is None else on_device(device):
             rc = self.fn(rx, rx_ld, tx, tx_ld, *front, *get("dec", no_T), *get("msg", self.no_K), *get("enc", no_T),
-                         *get("label_word", no_T), *get("labels", no_T), nerr, R, T, self.nsym, 1 if pilot else 0, 16, *tail,
+                         *get("label_word", no_T), *get("labels", no_T), nerr, R, T, self.nsym, 1 if pilot else 0, self.n_states, *tail,
                          current_stream(device) if stream is None else stream)
         if rc:
             check(rc, self.name)

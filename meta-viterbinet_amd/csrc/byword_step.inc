@@ -155,7 +155,8 @@ __device__ __forceinline__ void byword_encode_row(StepShared<NS> &sh, int lane, 
 // Everything of a block step after the detection, by ONE wave (the caller's): sh.dbits holds the detected word (data step),
 // sh.txrow the transmitted message as bytes, sh.gf the tables (and sh.gen the generator polynomial when NS > 2); word r's
 // outputs as in mvn_vnet_byword_step_f32.  CHOSEN (the list step, below): sh.row already holds the codeword to report.
-template <int NS, bool CHOSEN = false>
+// MEM: the memory length of the trellis whose states label the word (byword_step_states.inc: log2 of its state count).
+template <int NS, bool CHOSEN = false, int MEM = kStepMemory>
 __device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int lane, StepOut out, int T, int nsym, int pilot) {
     unsigned char *row = sh.row, *txrow = sh.txrow, *dbits = sh.dbits, *lwb = sh.lwb;
     const int n = T >> 3, k = n - nsym;
@@ -184,7 +185,7 @@ __device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int 
     // ---- encoded word, label word (trainer.py:322-324) and its trellis states
     const bool use_detected = nerr > 0;
     float *eb = out.enc ? out.enc + r * out.enc_ld : nullptr, *lb = out.label_word ? out.label_word + r * out.lw_ld : nullptr;
-    for (int t = lane; t < T + kStepMemory; t += 64) {
+    for (int t = lane; t < T + MEM; t += 64) {
         int ebit = 0, lbit = 0;
         if (t < T) {
             ebit = (row[t >> 3] >> (7 - (t & 7))) & 1;
@@ -200,7 +201,7 @@ __device__ __forceinline__ void byword_codec(StepShared<NS> &sh, int64_t r, int 
         for (int t = lane; t < T; t += 64) {
             int st = 0;
 #pragma unroll
-            for (int i = 0; i < kStepMemory; ++i) st |= (int)lwb[t + i] << i;  // state[t] = sum_i 2^i b[t + i]
+            for (int i = 0; i < MEM; ++i) st |= (int)lwb[t + i] << i;  // state[t] = sum_i 2^i b[t + i]
             lab[t] = st;
         }
     }

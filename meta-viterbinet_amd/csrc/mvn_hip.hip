@@ -17,6 +17,7 @@
 //   sweep_inplace.inc                      the same sweep for any other S >= 4 (in-place recurrence + LDS-DMA)
 //   va16_quad.inc, va_inplace.inc          fused classical Viterbi (16 states; any S >= 4)
 //   rs_codec.inc                           Reed-Solomon encode/decode
+//   byword_step.inc, byword_step_states.inc  one block step of the by-word evaluation in one launch (16 states; 4 ... 128 states)
 //   online_train.inc, maml_train.inc       one-launch online training and MAML meta-learning steps
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -278,28 +279,25 @@ int launch_sweep(const float *src, int64_t src_ld, const float *priors, int64_t 
 // -------------------------------------------------------------------------------------------
 constexpr int kMlpWaves = 4;
 
+// The tile's parts, shared as code by mlp_kernel and the block step at other state counts (byword_step_states.inc): same operations
+// in the same order, so the logits of both are the same bits.
+// W3 in A-operand order, element (j3,i3,lane) = W3[16*j3 + (lane&15)][4*i3 + (lane>>4)], and b3, by all threads of the workgroup
 template <int NT3>
-__global__ __launch_bounds__(64 * kMlpWaves, 2) void mlp_kernel(
-    const float *__restrict__ y, int64_t y_ld, int T, int64_t N, const float *__restrict__ W1,
-    const float *__restrict__ b1, const float *__restrict__ W2, const float *__restrict__ b2,
-    const float *__restrict__ W3, const float *__restrict__ b3, float *__restrict__ out, int S) {
-    __shared__ float ldsA3[NT3 * kK3Steps * 64];
-    __shared__ float ldsB3[NT3 * 16];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int j = lane & 15;
-    const int q = lane >> 4;
-
-    // stage W3 in A-operand order: element (j3,i3,lane) = W3[16*j3 + (lane&15)][4*i3 + (lane>>4)]
+__device__ __forceinline__ void mlp_stage_w3(float *ldsA3, float *ldsB3, const float *__restrict__ W3,
+                                             const float *__restrict__ b3, int S) {
     for (int e = threadIdx.x; e < NT3 * kK3Steps * 64; e += blockDim.x) {
         int l = e & 63, i3 = (e >> 6) % kK3Steps, j3 = (e >> 6) / kK3Steps;
         int st = 16 * j3 + (l & 15), k = 4 * i3 + (l >> 4);
         ldsA3[e] = (st < S && k < kH2) ? W3[st * kH2 + k] : 0.0f;
     }
     for (int e = threadIdx.x; e < NT3 * 16; e += blockDim.x) ldsB3[e] = e < S ? b3[e] : 0.0f;
+}
 
-    float nw1[kK2Steps], nb1[kK2Steps], a2[4][kK2Steps], b2v[4][4];
+// a lane's share of layers 1 and 2, held in registers for the kernel's lifetime
+__device__ __forceinline__ void mlp_load_weights(const float *__restrict__ W1, const float *__restrict__ b1,
+                                                 const float *__restrict__ W2, const float *__restrict__ b2, int j, int q,
+                                                 float (&nw1)[kK2Steps], float (&nb1)[kK2Steps], float (&a2)[4][kK2Steps],
+                                                 float (&b2v)[4][4]) {
 #pragma unroll
     for (int i = 0; i < kK2Steps; ++i) {
         nw1[i] = -W1[4 * i + q];
@@ -316,6 +314,86 @@ __global__ __launch_bounds__(64 * kMlpWaves, 2) void mlp_kernel(
             b2v[tau][r] = u < kH2 ? b2[u] : 0.0f;
         }
     }
+}
+
+// One tile: the lane's symbol yj through layers 1 and 2, then for every 16-state tile j3 of layer 3 store(j3, acc3), acc3[r] = the
+// logit of state 16 j3 + 4 q + r WITHOUT its bias for symbol j (the D layout); the caller adds b3 and stores.
+template <int NT3, class Store>
+__device__ __forceinline__ void mlp_tile(float yj, const float (&nw1)[kK2Steps], const float (&nb1)[kK2Steps],
+                                         const float (&a2)[4][kK2Steps], const float (&b2v)[4][4], const float *ldsA3, int lane,
+                                         Store store) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int tau = 0; tau < 4; ++tau) acc[tau] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < kK2Steps; ++i) {
+        // -(fma(y,w1,b1)) == fma(y,-w1,-b1): the argument of exp in torch's sigmoid
+        float h = sigmoid_from_neg(__builtin_fmaf(yj, nw1[i], nb1[i]));
+#pragma unroll
+        for (int tau = 0; tau < 4; ++tau)
+            acc[tau] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[tau][i], h, acc[tau], 0, 0, 0);
+    }
+
+    // bias + ReLU in D layout, then (q,r) transpose into B-operand order: bop[4*tau+r'] at
+    // lane (j,q) = h2[unit 16*tau + 4*r' + q][symbol j]
+    float bop[16];
+#pragma unroll
+    for (int tau = 0; tau < 4; ++tau) {
+        unsigned u[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float z = acc[tau][r] + b2v[tau][r];
+            u[r] = __float_as_uint(z < 0.0f ? 0.0f : z)  /* relu; NaN propagates like torch's */;
+        }
+        u32x2 p;
+        p = __builtin_amdgcn_permlane32_swap(u[0], u[2], false, false);
+        u[0] = p[0];
+        u[2] = p[1];
+        p = __builtin_amdgcn_permlane32_swap(u[1], u[3], false, false);
+        u[1] = p[0];
+        u[3] = p[1];
+        p = __builtin_amdgcn_permlane16_swap(u[0], u[1], false, false);
+        u[0] = p[0];
+        u[1] = p[1];
+        p = __builtin_amdgcn_permlane16_swap(u[2], u[3], false, false);
+        u[2] = p[0];
+        u[3] = p[1];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bop[4 * tau + r] = __uint_as_float(u[r]);
+    }
+
+    auto out_tile = [&](int j3) {
+        f32x4 acc3 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i3 = 0; i3 < kK3Steps; ++i3)
+            acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(ldsA3[(j3 * kK3Steps + i3) * 64 + lane], bop[i3], acc3, 0, 0, 0);
+        store(j3, acc3);
+    };
+    if constexpr (NT3 <= 2) {
+#pragma unroll
+        for (int j3 = 0; j3 < NT3; ++j3) out_tile(j3);
+    } else {
+#pragma unroll 1
+        for (int j3 = 0; j3 < NT3; ++j3) out_tile(j3);
+    }
+}
+
+template <int NT3>
+__global__ __launch_bounds__(64 * kMlpWaves, 2) void mlp_kernel(
+    const float *__restrict__ y, int64_t y_ld, int T, int64_t N, const float *__restrict__ W1,
+    const float *__restrict__ b1, const float *__restrict__ W2, const float *__restrict__ b2,
+    const float *__restrict__ W3, const float *__restrict__ b3, float *__restrict__ out, int S) {
+    __shared__ float ldsA3[NT3 * kK3Steps * 64];
+    __shared__ float ldsB3[NT3 * 16];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int j = lane & 15;
+    const int q = lane >> 4;
+
+    mlp_stage_w3<NT3>(ldsA3, ldsB3, W3, b3, S);
+    float nw1[kK2Steps], nb1[kK2Steps], a2[4][kK2Steps], b2v[4][4];
+    mlp_load_weights(W1, b1, W2, b2, j, q, nw1, nb1, a2, b2v);
     __syncthreads();
 
     const int64_t ntiles = (N + 15) / 16;
@@ -324,53 +402,7 @@ __global__ __launch_bounds__(64 * kMlpWaves, 2) void mlp_kernel(
         const int64_t n = tile * 16 + j;
         const int64_t nc = n < N ? n : N - 1;
         const float yj = y[(nc / T) * y_ld + (nc % T)];
-
-        f32x4 acc[4];
-#pragma unroll
-        for (int tau = 0; tau < 4; ++tau) acc[tau] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < kK2Steps; ++i) {
-            // -(fma(y,w1,b1)) == fma(y,-w1,-b1): the argument of exp in torch's sigmoid
-            float h = sigmoid_from_neg(__builtin_fmaf(yj, nw1[i], nb1[i]));
-#pragma unroll
-            for (int tau = 0; tau < 4; ++tau)
-                acc[tau] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[tau][i], h, acc[tau], 0, 0, 0);
-        }
-
-        // bias + ReLU in D layout, then (q,r) transpose into B-operand order: bop[4*tau+r'] at
-        // lane (j,q) = h2[unit 16*tau + 4*r' + q][symbol j]
-        float bop[16];
-#pragma unroll
-        for (int tau = 0; tau < 4; ++tau) {
-            unsigned u[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float z = acc[tau][r] + b2v[tau][r];
-                u[r] = __float_as_uint(z < 0.0f ? 0.0f : z)  /* relu; NaN propagates like torch's */;
-            }
-            u32x2 p;
-            p = __builtin_amdgcn_permlane32_swap(u[0], u[2], false, false);
-            u[0] = p[0];
-            u[2] = p[1];
-            p = __builtin_amdgcn_permlane32_swap(u[1], u[3], false, false);
-            u[1] = p[0];
-            u[3] = p[1];
-            p = __builtin_amdgcn_permlane16_swap(u[0], u[1], false, false);
-            u[0] = p[0];
-            u[1] = p[1];
-            p = __builtin_amdgcn_permlane16_swap(u[2], u[3], false, false);
-            u[2] = p[0];
-            u[3] = p[1];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) bop[4 * tau + r] = __uint_as_float(u[r]);
-        }
-
-        auto out_tile = [&](int j3) {
-            f32x4 acc3 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i3 = 0; i3 < kK3Steps; ++i3)
-                acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(ldsA3[(j3 * kK3Steps + i3) * 64 + lane], bop[i3],
-                                                            acc3, 0, 0, 0);
+        mlp_tile<NT3>(yj, nw1, nb1, a2, b2v, ldsA3, lane, [&](int j3, f32x4 acc3) {
             const int st0 = 16 * j3 + 4 * q;
             if (n < N) {
                 float *o = out + n * S + st0;
@@ -387,14 +419,7 @@ __global__ __launch_bounds__(64 * kMlpWaves, 2) void mlp_kernel(
                         if (st0 + r < S) o[r] = acc3[r] + ldsB3[st0 + r];
                 }
             }
-        };
-        if constexpr (NT3 <= 2) {
-#pragma unroll
-            for (int j3 = 0; j3 < NT3; ++j3) out_tile(j3);
-        } else {
-#pragma unroll 1
-            for (int j3 = 0; j3 < NT3; ++j3) out_tile(j3);
-        }
+        });
     }
 }
 
@@ -445,6 +470,7 @@ int ensure_dynamic_lds(const void *fn, size_t bytes);  // raises a kernel's dyna
 #include "vnet_fused_ip.inc"
 #include "rs_codec.inc"
 #include "byword_step.inc"
+#include "byword_step_states.inc"
 #include "online_train.inc"
 #include "maml_train.inc"
 #include "train_groups.inc"
@@ -1164,7 +1190,7 @@ int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *man
 #include "lstm.inc"
 #include "lstm_train.inc"
 
-// ---- the by-word block steps (byword_step.inc).  What the six entry points share: they only fill this
+// ---- the by-word block steps (byword_step.inc, byword_step_states.inc).  What the entry points share: they only fill this
 enum StepDetector { kStepVnet, kStepVa };
 struct StepCall {
     const float *rx; int64_t rx_ld;
@@ -1194,16 +1220,32 @@ int list_step_candidates(int32_t T, int32_t nsym, int32_t m) {
     return c <= kListMaxCand ? (int)c : 0;
 }
 
+// the longest word mvn_vnet_byword_step_states_f32 serves at S states (0: a state count it does not serve; 16 states: the step it
+// forwards to)
+int states_step_max_symbols(int32_t S) {
+    switch (S) {
+        case 4: return states_max_symbols<4>();
+        case 8: return states_max_symbols<8>();
+        case 16: return kCoopMaxT;
+        case 32: return states_max_symbols<32>();
+        case 64: return states_max_symbols<64>();
+        case 128: return states_max_symbols<128>();
+        default: return 0;
+    }
+}
+
 // The checks of a step, in the order the codes are documented in: the state count; the shapes; the list's limits; every leading
 // dimension; the rows of priors (VA); nothing to do (R = 0: MVN_OK before any pointer is looked at); the pointers.  A pilot detects
 // nothing, so a pilot of any decision is the running step and is checked as one: it needs tx and neither rx nor the priors (the
 // ViterbiNet weights are required all the same); only a list data step can do without tx, as long as nothing is compared with it.
-// Leaves the list's number of candidates in c.list.ncand.
-int step_check(StepCall &c, StepDecision decision, StepDetector detector) {
+// Leaves the list's number of candidates in c.list.ncand.  any_states: the ViterbiNet running step of byword_step_states.inc, whose
+// state counts and longest word are states_step_max_symbols'.
+int step_check(StepCall &c, StepDecision decision, StepDetector detector, bool any_states = false) {
     const StepOut &o = c.out;
     const int T = c.T, nsym = c.nsym;
-    if (c.S != 16) return MVN_E_STATES;  // the fused step exists for the 16-state detectors
-    if (c.R < 0 || T < 8 || (T & 7) || T > kCoopMaxT || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
+    const int max_T = any_states ? states_step_max_symbols(c.S) : kCoopMaxT;
+    if (any_states ? max_T == 0 : c.S != 16) return MVN_E_STATES;  // (the six steps of byword_step.inc exist for the 16-state detectors)
+    if (c.R < 0 || T < 8 || (T & 7) || T > max_T || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
     if (decision == kStepList) {
         c.list.ncand = list_step_candidates(T, nsym, c.list.m);
         if (c.list.ncand == 0 || (c.list.delta && c.list.delta_ld < T)) return MVN_E_DIMS;
@@ -1271,6 +1313,33 @@ int step_run(StepCall c, StepDecision decision, StepDetector detector) {
                            std::tuple_cat(head, path));
     return step_launch(byword_list_step_kernel<2>, byword_list_step_kernel<8>, c, threads, tiles * 2048, list_max,
                        std::tuple_cat(head, list));
+}
+
+// mvn_vnet_byword_step_states_f32 at S != 16: one launch of byword_step_states_kernel<S, NS>, R workgroups of kStatesWaves waves, the
+// logit image (a data step's) as dynamic LDS
+template <int S, class Args>
+int states_step_launch(const StepCall &c, const Args &args) {
+    return step_launch(byword_step_states_kernel<S, 2>, byword_step_states_kernel<S, 8>, c, 64 * kStatesWaves,
+                       c.pilot ? 0 : (size_t)c.T * S * sizeof(float), (size_t)states_max_symbols<S>() * S * sizeof(float), args);
+}
+
+int states_step_run(StepCall c) {
+    const int e = step_check(c, kStepRunning, kStepVnet, true);
+    if (e != MVN_OK || c.R == 0) return e;
+    const StepOut &o = c.out;
+    WeightStrides ws;
+    for (int a = 0; a < 6; ++a) ws.s[a] = c.w_stride ? (long long)c.w_stride[a] : 0;
+    const auto args = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.W[0], c.W[1], c.W[2], c.W[3], c.W[4], c.W[5], ws, c.dec, c.dec_ld,
+                                      o.msg, o.msg_ld, o.enc, o.enc_ld, o.label_word, o.lw_ld, o.labels, o.lab_ld, o.nerr, c.T, c.nsym,
+                                      c.pilot);
+    switch (c.S) {
+        case 4: return states_step_launch<4>(c, args);
+        case 8: return states_step_launch<8>(c, args);
+        case 32: return states_step_launch<32>(c, args);
+        case 64: return states_step_launch<64>(c, args);
+        case 128: return states_step_launch<128>(c, args);
+        default: return MVN_E_STATES;
+    }
 }
 
 }  // namespace
@@ -1700,6 +1769,20 @@ int mvn_vnet_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, in
     return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
                      {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
                     kStepRunning, kStepVnet);
+}
+
+int32_t mvn_vnet_byword_step_max_symbols(int32_t S) { return states_step_max_symbols(S); }
+
+int mvn_vnet_byword_step_states_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                    const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                    float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                    float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                    int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    if (S == 16)  // one call for every state count: the 16-state step, with its own checks
+        return mvn_vnet_byword_step_f32(rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
+                                        label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    return states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                            {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream});
 }
 
 int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,

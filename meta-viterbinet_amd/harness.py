@@ -274,6 +274,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     generators (the reference's are unseeded), which is what makes a run replayable inside trials.eval_by_word_batched.
     fused_step: a 16-state ViterbiNet detector with nsym <= 8 takes ONE launch per block (mvn_vnet_byword_step_f32:
     detect, RS decode, error count, re-encode); False keeps the four separate launches (the cross-check in the tests).
+    So does a ViterbiNet detector at 4, 8, 32, 64 or 128 states with the running decision (mvn_vnet_byword_step_states_f32, words
+    up to _lib.step_max_symbols(n_states) symbols); decision='path' at those state counts keeps the separate launches.
     observer: called at the end of every block of the update branches with a dict {stage: 'end', count, ser, pushed,
     buffer_rx, buffer_tx, meta: (support_idx [n, W], query_idx [n]) or None, trained, batch_idx, detector, saved_detector},
     and with stage 'meta' right after a meta-learning update launched by the HIP kernel: what a test needs to replay the
@@ -317,7 +319,7 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     N = tx.shape[0]
     ser_by_word = np.zeros(N)
     K = tx.shape[1]
-    fused = fused_step and _fused_step_applies(detector, rx, n_symbols, pass_count)
+    fused = fused_step and _fused_step_applies(detector, rx, n_symbols, pass_count, decision)
     if decision == "list":
         list_bytes = _list_step_bytes(detector, rx, n_symbols, pass_count, fused_step, list_bytes)
     elif list_bytes is not None:
@@ -387,7 +389,9 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     # The fused ViterbiNet step also picks the word the reference buffers and computes its trellis states (what the training
     # kernels take as labels), and the block's error count travels to the host together with the trainer's status word: one
     # launch and one 8-byte copy per block before the host decides.
-    step_labels = fused and isinstance(detector, VNETDetector) and online_trainer is not None and online_trainer.use_kernel
+    # (the step's states are those of the detector's own trellis, memory length log2 n_states)
+    step_labels = (fused and isinstance(detector, VNETDetector) and online_trainer is not None and online_trainer.use_kernel
+                   and 2 ** online_trainer.memory_length == detector.n_states)
     sync_words = online_trainer.sync_words if (step_labels and getattr(online_trainer, "sync_words", None) is not None) else None
     nerr1 = (sync_words[:1] if sync_words is not None else torch.zeros(1, dtype=torch.int32, device=rx.device)) if fused else None
     buffer_lab = None
@@ -514,16 +518,23 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     return ser_by_word
 
 
-def _fused_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool) -> bool:
+def _fused_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, decision: str = "running") -> bool:
     """One launch per block step (mvn_vnet_byword_step_f32 / mvn_va_byword_step_f32) serves a 16-state VNETDetector or
     VADetector whose 'val' length is the word length (Q5), words of whole bytes up to 1024 symbols and nsym <= 8; everything
     else takes the separate detect / RS / count launches.  (pass_count: the reference passes the block number to the detector,
-    which is how VADetector picks the word's channel; ViterbiNet ignores it.)"""
+    which is how VADetector picks the word's channel; ViterbiNet ignores it.)
+    A VNETDetector at 4, 8, 32, 64 or 128 states has the step for the running decision (mvn_vnet_byword_step_states_f32), for words
+    up to _lib.step_max_symbols(n_states) symbols."""
+    from . import _lib
     from .detectors import VADetector, VNETDetector
 
     T = rx.shape[1]
-    if not (rx.is_cuda and getattr(detector, "n_states", None) == 16 and T % 8 == 0 and 8 <= T <= 1024 and 1 <= n_symbols <= 8 and T // 8 > n_symbols):
+    S = getattr(detector, "n_states", None)
+    if not (rx.is_cuda and T % 8 == 0 and 8 <= T <= 1024 and 1 <= n_symbols <= 8 and T // 8 > n_symbols):
         return False
+    if S != 16:
+        return (S in _lib.STEP_STATES and isinstance(detector, VNETDetector) and decision == "running" and not pass_count
+                and detector.transmission_lengths["val"] == T and T <= _lib.step_max_symbols(S))
     if isinstance(detector, VNETDetector):
         return not pass_count and detector.transmission_lengths["val"] == T
     # VADetector: the fused step takes ONE row of state priors -- the word's own (pass_count) or the table's only row.  A
@@ -566,7 +577,8 @@ def _block_step(detector, T: int, n_symbols: int, decision: str, list_bytes):
     from . import _lib
     from .detectors import VADetector
 
-    return _lib.BywordStep("va" if isinstance(detector, VADetector) else "vnet", decision, T, n_symbols, list_bytes)
+    return _lib.BywordStep("va" if isinstance(detector, VADetector) else "vnet", decision, T, n_symbols, list_bytes,
+                           n_states=detector.n_states)
 
 
 def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, pilot: bool, nerr: torch.Tensor,

@@ -6,8 +6,9 @@ the (SNR x seed x method) grid the reference walks serially (plotters/plotter_ma
 MI355X's 256 CUs; here R trials step through their blocks together:
 
     per block step:  ONE mvn_vnet_byword_step_f32 launch (detect + RS decode + error count + re-encode + labels for all R
-                     words, each with its own weights)  ->  ONE device-to-host copy of the R error counts (the only sync:
-                     every trial's next move depends on its coded ser, trainer.py:305,319)  ->  per-trial decisions on the
+                     words, each with its own weights; mvn_vnet_byword_step_states_f32 at 4, 8, 32, 64 and 128 states)  ->
+                     ONE device-to-host copy of the R error counts (the only sync: every trial's next move depends on its
+                     coded ser, trainer.py:305,319)  ->  per-trial decisions on the
                      host  ->  at most ONE mvn_vnet_maml_train_trials_f32 and ONE mvn_vnet_online_train_trials_f32 launch
                      sequence for the trials that train (gridDim.y = trial, per-trial barrier counters).
 
@@ -210,8 +211,10 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     bank.optimizer_type 'RMSprop' / 'SGD' (deep_learning_setup, :163-175): the online-training kernel implements them next to
     Adam, the reference's default (round 5); the meta-learning kernel implements Adam, so a run with online_meta and another
     optimizer goes trial after trial through harness.eval_by_word (its meta-learning updates on stock autograd) -- same results as
-    calling it yourself, no batching.  So do detectors with another state count than 16 (the one-launch block step and its
-    R-word form serve 16 states): trial after trial through harness.eval_by_word, there on the run-time-n_states training kernels.
+    calling it yourself, no batching.  Banks at 4, 8, 32, 64 and 128 states take the lock-step engine with the running decision
+    (mvn_vnet_byword_step_states_f32 for all R trials, words up to _lib.step_max_symbols(n_states) symbols, the run-time-n_states
+    training kernels); what goes trial after trial through harness.eval_by_word there: online_meta above 32 states (the
+    meta-learning kernel's limit), decision='path', longer words, and every other state count.
     cohorts > 1: the trials are split into that many groups that step ALTERNATELY on the same stream: while the GPU works
     through one group's training launches the host takes the decisions and fills the descriptors of the next (the host
     work of a step can only start after the step's sync).  Same launches per trial, same results.
@@ -269,7 +272,7 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
                                         ser_thresh, online_meta, meta_lr, MAML, window_size, meta_train_iterations, meta_j_num,
                                         meta_subframes, meta_style_online_training, weights_init, meta_training_weights, record,
                                         initial_buffer)
-    if (bank.optimizer_type != "Adam" and online_meta) or bank.n_states != 16:
+    if (bank.optimizer_type != "Adam" and online_meta) or not _lock_step_serves(bank.n_states, rx, n_symbols, decision, online_meta):
         return _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, initial_buffer,
                                     dict(self_supervised=self_supervised, self_supervised_iterations=self_supervised_iterations,
                                          ser_thresh=ser_thresh, online_meta=online_meta, meta_lr=meta_lr, MAML=MAML, window_size=window_size,
@@ -301,11 +304,22 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     return ser_by_word
 
 
+def _lock_step_serves(n_states: int, rx: torch.Tensor, n_symbols: int, decision: str, online_meta: bool) -> bool:
+    """Whether the lock-step engine has its kernels for this bank: the six 16-state block steps, or at 4, 8, 32, 64 and 128 states
+    the running step for words it takes (whole bytes, nsym <= 8, no longer than it can hold), with meta-learning up to the 32 states
+    of mvn_vnet_maml_train_trials_f32."""
+    if n_states == 16:
+        return True
+    T = rx.shape[2]
+    return (n_states in _lib.STEP_STATES and decision == "running" and rx.is_cuda and T % 8 == 0 and 1 <= n_symbols <= 8
+            and T // 8 > n_symbols and T <= _lib.step_max_symbols(n_states) and not (online_meta and n_states > 32))
+
+
 def _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, initial_buffer, kw,
                          train_minibatch_size):
     """The trials of a bank the lock-step engine does not serve -- meta-learning with an optimizer its kernel does not implement
-    (RMSprop, SGD) or another state count than 16 (no R-word block step) -- one after the other through harness.eval_by_word;
-    weights, saved weights, optimizer state and step counts go back into the bank."""
+    (RMSprop, SGD) or above 32 states, a state count or a decision without an R-word block step (_lock_step_serves) -- one after the
+    other through harness.eval_by_word; weights, saved weights, optimizer state and step counts go back into the bank."""
     from .detectors import META_VNETDetector, VNETDetector
     from .harness import eval_by_word
     from .online import OnlineTrainer
@@ -349,11 +363,9 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
                   initial_buffer=None, decision="running", list_bytes=None):
     """One group of trials stepping through its blocks: a generator that enqueues a step's GPU work and yields the event the
     host has to wait for before it can decide what the trials do next (eval_by_word_batched drives one or more of these)."""
-    if bank.n_states != 16:
-        raise NotImplementedError("the batched evaluation runs the 16-state kernels (mvn_vnet_byword_step_f32)")
     _lib.require_gpu_tensor(rx, "rx")
     lib = _lib.load()
-    step = _lib.BywordStep("vnet", decision, rx.shape[2], n_symbols, list_bytes)
+    step = _lib.BywordStep("vnet", decision, rx.shape[2], n_symbols, list_bytes, n_states=bank.n_states)
     dev = rx.device
     R, N, T = rx.shape
     K = tx.shape[2]
