@@ -394,6 +394,23 @@ int mvn_vnet_byword_step_states_f32(const float *rx, int64_t rx_ld, const float 
                                     int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
 
 /*
+ * mvn_vnet_byword_step_states_f32 on the TRACED-BACK path: mvn_vnet_byword_step_path_f32 (below) for the ViterbiNet detector at
+ * S = 4, 8, 32, 64 or 128 states (S = 16 forwards to it).  Same arguments, same check and codes in the same order, same longest word
+ * mvn_vnet_byword_step_max_symbols(S), same outputs, one launch.  On a data step dec is bit-identical to mvn_vnet_logits_f32 ->
+ * mvn_acs_sweep_surv_f32 -> mvn_traceback_f32 (= mvn_vnet_decode_surv_f32 -> mvn_traceback_f32): survivor = torch.min's index (the
+ * first minimum, the first NaN), the walk starts at torch.argmin of the final metric (a NaN counting as minimal), dec[t] = the
+ * least-significant bit of the path's state before stage t; msg, nerr, enc, label_word and labels follow from that dec as in
+ * mvn_vnet_byword_step_states_f32.  The survivors take the place of the logits in the on-chip image, a word per stage (states s and
+ * s + S / 2 share their predecessors and so their bit), and never leave the chip.  A pilot step detects nothing: it IS
+ * mvn_vnet_byword_step_states_f32's pilot step.  (Added without a bump of MVN_ABI_VERSION, like the other steps.)
+ */
+int mvn_vnet_byword_step_states_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                         const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                         float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                         float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                         int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+
+/*
  * The same block step for the classical Viterbi detector (the reference's eval_by_word takes any detector, trainer.py:295):
  * dec = VADetector.forward(rx, 'val', snr, gamma, count) with the state priors given as in mvn_va_decode_f32 -- word r uses
  * row r % Bp of state_priors [Bp, 16] (compute_state_priors, va_detector.py:42-50, of the word's channel) -- then exactly

@@ -64,6 +64,7 @@ SIGNATURES = {
     "mvn_vnet_byword_step_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_vnet_byword_step_max_symbols": (_i32, [_i32]),
     "mvn_vnet_byword_step_states_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_vnet_byword_step_states_path_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_va_byword_step_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_vnet_byword_step_path_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_va_byword_step_path_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
@@ -161,11 +162,11 @@ def current_stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-STEP_STATES = (4, 8, 32, 64, 128)  # the state counts of mvn_vnet_byword_step_states_f32, next to the 16 of the six steps
+STEP_STATES = (4, 8, 32, 64, 128)  # the state counts of mvn_vnet_byword_step_states[_path]_f32, next to the 16 of the six steps
 
 
 def step_max_symbols(n_states: int) -> int:
-    """The longest word the ViterbiNet running step serves at n_states (mvn_vnet_byword_step_max_symbols; 0: not served)."""
+    """The longest word the ViterbiNet running and path steps serve at n_states (mvn_vnet_byword_step_max_symbols; 0: not served)."""
     return int(load().mvn_vnet_byword_step_max_symbols(n_states))
 
 
@@ -173,14 +174,15 @@ class BywordStep:
     """One of the by-word block steps of include/mvn.h, mvn_{kind}_byword_step[_path|_list]_f32 (kind 'vnet' / 'va', decision
     'running' / 'path' / 'list'), for words of T symbols with nsym parity bytes (list: list_bytes least reliable bytes): the symbol
     and the constant part of its argument list are resolved here, once, outside a caller's block loop.
-    n_states other than 16: mvn_vnet_byword_step_states_f32, which exists for the ViterbiNet running step only (ValueError else)."""
-    def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None, n_states: int = 16):
+    n_states other than 16: mvn_vnet_byword_step_states_f32, the ViterbiNet running step, and with states_path=True (what
+    harness._block_step and trials._cohort_steps pass) mvn_vnet_byword_step_states_path_f32 for decision 'path'; ValueError else."""
+    def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None, n_states: int = 16, states_path: bool = False):
         self.name = "mvn_%s_byword_step%s_f32" % (kind, {"running": "", "path": "_path", "list": "_list"}[decision])
         if n_states != 16:
-            if kind != "vnet" or decision != "running":
-                raise ValueError(f"the block step at {n_states} states is the ViterbiNet running step (kind='vnet', decision='running'), "
-                                 f"not kind={kind!r}, decision={decision!r}")
-            self.name = "mvn_vnet_byword_step_states_f32"
+            if kind != "vnet" or decision not in (("running", "path") if states_path else ("running",)):
+                raise ValueError(f"the block step at {n_states} states is the ViterbiNet running step (kind='vnet', decision='running'; "
+                                 f"states_path=True: decision='path' as well), not kind={kind!r}, decision={decision!r}")
+            self.name = "mvn_vnet_byword_step_states%s_f32" % ("_path" if decision == "path" else "")
         self.n_states = n_states
         self.fn = getattr(load(), self.name)
         self.no_T, self.no_K = (None, T), (None, T - 8 * nsym)  # an output that is not asked for, with its row's length

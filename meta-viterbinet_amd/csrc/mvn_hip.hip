@@ -1220,8 +1220,8 @@ int list_step_candidates(int32_t T, int32_t nsym, int32_t m) {
     return c <= kListMaxCand ? (int)c : 0;
 }
 
-// the longest word mvn_vnet_byword_step_states_f32 serves at S states (0: a state count it does not serve; 16 states: the step it
-// forwards to)
+// the longest word mvn_vnet_byword_step_states_f32 and mvn_vnet_byword_step_states_path_f32 serve at S states (0: a state count
+// they do not serve; 16 states: the steps they forward to)
 int states_step_max_symbols(int32_t S) {
     switch (S) {
         case 4: return states_max_symbols<4>();
@@ -1238,8 +1238,8 @@ int states_step_max_symbols(int32_t S) {
 // dimension; the rows of priors (VA); nothing to do (R = 0: MVN_OK before any pointer is looked at); the pointers.  A pilot detects
 // nothing, so a pilot of any decision is the running step and is checked as one: it needs tx and neither rx nor the priors (the
 // ViterbiNet weights are required all the same); only a list data step can do without tx, as long as nothing is compared with it.
-// Leaves the list's number of candidates in c.list.ncand.  any_states: the ViterbiNet running step of byword_step_states.inc, whose
-// state counts and longest word are states_step_max_symbols'.
+// Leaves the list's number of candidates in c.list.ncand.  any_states: the ViterbiNet running and path steps of
+// byword_step_states.inc, whose state counts and longest word are states_step_max_symbols'.
 int step_check(StepCall &c, StepDecision decision, StepDetector detector, bool any_states = false) {
     const StepOut &o = c.out;
     const int T = c.T, nsym = c.nsym;
@@ -1315,29 +1315,33 @@ int step_run(StepCall c, StepDecision decision, StepDetector detector) {
                        std::tuple_cat(head, list));
 }
 
-// mvn_vnet_byword_step_states_f32 at S != 16: one launch of byword_step_states_kernel<S, NS>, R workgroups of kStatesWaves waves, the
-// logit image (a data step's) as dynamic LDS
-template <int S, class Args>
-int states_step_launch(const StepCall &c, const Args &args) {
-    return step_launch(byword_step_states_kernel<S, 2>, byword_step_states_kernel<S, 8>, c, 64 * kStatesWaves,
-                       c.pilot ? 0 : (size_t)c.T * S * sizeof(float), (size_t)states_max_symbols<S>() * S * sizeof(float), args);
+// mvn_vnet_byword_step_states_f32 / mvn_vnet_byword_step_states_path_f32 at S != 16: one launch of byword_step_states_kernel<S, NS> or
+// byword_path_step_states_kernel<S, NS>, R workgroups of kStatesWaves waves, the logit image (a data step's) as dynamic LDS
+template <int S, class Head>
+int states_step_launch(const StepCall &c, StepDecision decision, const Head &head) {
+    const size_t dyn = c.pilot ? 0 : (size_t)c.T * S * sizeof(float), dyn_max = (size_t)states_max_symbols<S>() * S * sizeof(float);
+    if (decision == kStepPath)
+        return step_launch(byword_path_step_states_kernel<S, 2>, byword_path_step_states_kernel<S, 8>, c, 64 * kStatesWaves, dyn, dyn_max,
+                           std::tuple_cat(head, std::make_tuple(c.T, c.nsym)));
+    return step_launch(byword_step_states_kernel<S, 2>, byword_step_states_kernel<S, 8>, c, 64 * kStatesWaves, dyn, dyn_max,
+                       std::tuple_cat(head, std::make_tuple(c.T, c.nsym, c.pilot)));
 }
 
-int states_step_run(StepCall c) {
-    const int e = step_check(c, kStepRunning, kStepVnet, true);
+int states_step_run(StepCall c, StepDecision decision) {
+    const int e = step_check(c, decision, kStepVnet, true);
     if (e != MVN_OK || c.R == 0) return e;
+    if (c.pilot) decision = kStepRunning;  // (the path kernel is a data step)
     const StepOut &o = c.out;
     WeightStrides ws;
     for (int a = 0; a < 6; ++a) ws.s[a] = c.w_stride ? (long long)c.w_stride[a] : 0;
-    const auto args = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.W[0], c.W[1], c.W[2], c.W[3], c.W[4], c.W[5], ws, c.dec, c.dec_ld,
-                                      o.msg, o.msg_ld, o.enc, o.enc_ld, o.label_word, o.lw_ld, o.labels, o.lab_ld, o.nerr, c.T, c.nsym,
-                                      c.pilot);
+    const auto head = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.W[0], c.W[1], c.W[2], c.W[3], c.W[4], c.W[5], ws, c.dec, c.dec_ld,
+                                      o.msg, o.msg_ld, o.enc, o.enc_ld, o.label_word, o.lw_ld, o.labels, o.lab_ld, o.nerr);
     switch (c.S) {
-        case 4: return states_step_launch<4>(c, args);
-        case 8: return states_step_launch<8>(c, args);
-        case 32: return states_step_launch<32>(c, args);
-        case 64: return states_step_launch<64>(c, args);
-        case 128: return states_step_launch<128>(c, args);
+        case 4: return states_step_launch<4>(c, decision, head);
+        case 8: return states_step_launch<8>(c, decision, head);
+        case 32: return states_step_launch<32>(c, decision, head);
+        case 64: return states_step_launch<64>(c, decision, head);
+        case 128: return states_step_launch<128>(c, decision, head);
         default: return MVN_E_STATES;
     }
 }
@@ -1782,7 +1786,21 @@ int mvn_vnet_byword_step_states_f32(const float *rx, int64_t rx_ld, const float 
         return mvn_vnet_byword_step_f32(rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
                                         label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
     return states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
-                            {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream});
+                            {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
+                           kStepRunning);
+}
+
+int mvn_vnet_byword_step_states_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                         const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                         float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                         float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                         int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    if (S == 16)
+        return mvn_vnet_byword_step_path_f32(rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
+                                             label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    return states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                            {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
+                           kStepPath);
 }
 
 int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,

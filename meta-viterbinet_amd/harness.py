@@ -274,8 +274,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     generators (the reference's are unseeded), which is what makes a run replayable inside trials.eval_by_word_batched.
     fused_step: a 16-state ViterbiNet detector with nsym <= 8 takes ONE launch per block (mvn_vnet_byword_step_f32:
     detect, RS decode, error count, re-encode); False keeps the four separate launches (the cross-check in the tests).
-    So does a ViterbiNet detector at 4, 8, 32, 64 or 128 states with the running decision (mvn_vnet_byword_step_states_f32, words
-    up to _lib.step_max_symbols(n_states) symbols); decision='path' at those state counts keeps the separate launches.
+    So does a ViterbiNet detector at 4, 8, 32, 64 or 128 states with the running decision (mvn_vnet_byword_step_states_f32) and with
+    decision='path' (mvn_vnet_byword_step_states_path_f32), words up to _lib.step_max_symbols(n_states) symbols.
     observer: called at the end of every block of the update branches with a dict {stage: 'end', count, ser, pushed,
     buffer_rx, buffer_tx, meta: (support_idx [n, W], query_idx [n]) or None, trained, batch_idx, detector, saved_detector},
     and with stage 'meta' right after a meta-learning update launched by the HIP kernel: what a test needs to replay the
@@ -523,8 +523,9 @@ def _fused_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: 
     VADetector whose 'val' length is the word length (Q5), words of whole bytes up to 1024 symbols and nsym <= 8; everything
     else takes the separate detect / RS / count launches.  (pass_count: the reference passes the block number to the detector,
     which is how VADetector picks the word's channel; ViterbiNet ignores it.)
-    A VNETDetector at 4, 8, 32, 64 or 128 states has the step for the running decision (mvn_vnet_byword_step_states_f32), for words
-    up to _lib.step_max_symbols(n_states) symbols."""
+    A VNETDetector at 4, 8, 32, 64 or 128 states has the step for the running decision (mvn_vnet_byword_step_states_f32) and for the
+    traced-back path (mvn_vnet_byword_step_states_path_f32), for words up to _lib.step_max_symbols(n_states) symbols; 'list' is a
+    16-state step."""
     from . import _lib
     from .detectors import VADetector, VNETDetector
 
@@ -533,7 +534,7 @@ def _fused_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: 
     if not (rx.is_cuda and T % 8 == 0 and 8 <= T <= 1024 and 1 <= n_symbols <= 8 and T // 8 > n_symbols):
         return False
     if S != 16:
-        return (S in _lib.STEP_STATES and isinstance(detector, VNETDetector) and decision == "running" and not pass_count
+        return (S in _lib.STEP_STATES and isinstance(detector, VNETDetector) and decision in ("running", "path") and not pass_count
                 and detector.transmission_lengths["val"] == T and T <= _lib.step_max_symbols(S))
     if isinstance(detector, VNETDetector):
         return not pass_count and detector.transmission_lengths["val"] == T
@@ -578,7 +579,7 @@ def _block_step(detector, T: int, n_symbols: int, decision: str, list_bytes):
     from .detectors import VADetector
 
     return _lib.BywordStep("va" if isinstance(detector, VADetector) else "vnet", decision, T, n_symbols, list_bytes,
-                           n_states=detector.n_states)
+                           n_states=detector.n_states, states_path=True)
 
 
 def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, pilot: bool, nerr: torch.Tensor,

@@ -211,10 +211,11 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     bank.optimizer_type 'RMSprop' / 'SGD' (deep_learning_setup, :163-175): the online-training kernel implements them next to
     Adam, the reference's default (round 5); the meta-learning kernel implements Adam, so a run with online_meta and another
     optimizer goes trial after trial through harness.eval_by_word (its meta-learning updates on stock autograd) -- same results as
-    calling it yourself, no batching.  Banks at 4, 8, 32, 64 and 128 states take the lock-step engine with the running decision
-    (mvn_vnet_byword_step_states_f32 for all R trials, words up to _lib.step_max_symbols(n_states) symbols, the run-time-n_states
-    training kernels); what goes trial after trial through harness.eval_by_word there: online_meta above 32 states (the
-    meta-learning kernel's limit), decision='path', longer words, and every other state count.
+    calling it yourself, no batching.  Banks at 4, 8, 32, 64 and 128 states take the lock-step engine with the running decision and
+    with decision='path' (mvn_vnet_byword_step_states_f32 / mvn_vnet_byword_step_states_path_f32 for all R trials, words up to
+    _lib.step_max_symbols(n_states) symbols, the run-time-n_states training kernels); what goes trial after trial through
+    harness.eval_by_word there: online_meta above 32 states (the meta-learning kernel's limit), longer words, and every other state
+    count.
     cohorts > 1: the trials are split into that many groups that step ALTERNATELY on the same stream: while the GPU works
     through one group's training launches the host takes the decisions and fills the descriptors of the next (the host
     work of a step can only start after the step's sync).  Same launches per trial, same results.
@@ -229,8 +230,8 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     cohorts is accepted and ignored for an LSTM bank: a training launch takes hundreds of milliseconds, the host work of a step
     is not worth hiding behind it.
     decision='path': every block is detected by the traced-back maximum-likelihood word instead of the reference's running argmin
-    (harness.eval_by_word(decision='path')): the lock-step block step is mvn_vnet_byword_step_path_f32 for all R trials, the
-    trial-after-trial route passes the keyword on; an LSTM bank raises ValueError.
+    (harness.eval_by_word(decision='path')): the lock-step block step is mvn_vnet_byword_step_path_f32 for all R trials
+    (mvn_vnet_byword_step_states_path_f32 at 4, 8, 32, 64 and 128 states), the trial-after-trial route passes the keyword on; an LSTM bank raises ValueError.
     decision='list': the path's word, list-decoded in the same launch (mvn_vnet_byword_step_list_f32 for all R trials; list_bytes
     as in harness.eval_by_word, default n_symbols + 2).  It needs the 16-state step and words of at most 512 symbols: ValueError
     otherwise, there is no other route."""
@@ -306,12 +307,12 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
 
 def _lock_step_serves(n_states: int, rx: torch.Tensor, n_symbols: int, decision: str, online_meta: bool) -> bool:
     """Whether the lock-step engine has its kernels for this bank: the six 16-state block steps, or at 4, 8, 32, 64 and 128 states
-    the running step for words it takes (whole bytes, nsym <= 8, no longer than it can hold), with meta-learning up to the 32 states
-    of mvn_vnet_maml_train_trials_f32."""
+    the running step and the path step (not 'list') for words they take (whole bytes, nsym <= 8, no longer than they can hold), with
+    meta-learning up to the 32 states of mvn_vnet_maml_train_trials_f32."""
     if n_states == 16:
         return True
     T = rx.shape[2]
-    return (n_states in _lib.STEP_STATES and decision == "running" and rx.is_cuda and T % 8 == 0 and 1 <= n_symbols <= 8
+    return (n_states in _lib.STEP_STATES and decision in ("running", "path") and rx.is_cuda and T % 8 == 0 and 1 <= n_symbols <= 8
             and T // 8 > n_symbols and T <= _lib.step_max_symbols(n_states) and not (online_meta and n_states > 32))
 
 
@@ -365,7 +366,7 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
     host has to wait for before it can decide what the trials do next (eval_by_word_batched drives one or more of these)."""
     _lib.require_gpu_tensor(rx, "rx")
     lib = _lib.load()
-    step = _lib.BywordStep("vnet", decision, rx.shape[2], n_symbols, list_bytes, n_states=bank.n_states)
+    step = _lib.BywordStep("vnet", decision, rx.shape[2], n_symbols, list_bytes, n_states=bank.n_states, states_path=True)
     dev = rx.device
     R, N, T = rx.shape
     K = tx.shape[2]
