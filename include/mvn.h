@@ -262,8 +262,11 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
  *   rx_words [Nw, T] fp32 received words and labels [Nw, T] int32 trellis states (calculate_states of the buffered
  *   transmitted words); step k uses the W words support_idx[k*W .. k*W+W-1] and the word query_idx[k] (indices into
  *   the Nw words, already non-negative); weights, adam_m/adam_v [P] and step0 as in mvn_vnet_online_train_f32 (the
- *   reference has one optimizer for both loops); loss_out [n_steps] query losses or NULL.  S <= 32.
+ *   reference has one optimizer for both loops); loss_out [n_steps] query losses or NULL.  S <= 128.
  * fp32, deterministic; agrees with torch's double backward + Adam to rounding (tolerance in the tests).
+ * S = 64 and 128 (maml_train_kernel<64 | 128, false>, one workgroup): the LDS holds two parameter-sized vectors, so between
+ * the two gradient passes of a step the weights wait in W1 .. b3 themselves -- while the call runs these arrays hold
+ * intermediate values; no workspace is needed (mvn_vnet_train_workspace_bytes stays 0 there).
  */
 int mvn_vnet_maml_train_f32(const float *rx_words, const int32_t *labels, int32_t T, const int32_t *support_idx, int32_t W,
                             const int32_t *query_idx, int32_t n_steps, float *W1, float *b1, float *W2, float *b2,
@@ -335,6 +338,10 @@ int mvn_vnet_maml_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, i
  */
 int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_W, int32_t S, size_t workspace_bytes, char *name,
                                int32_t name_len);
+/* The dynamic LDS (bytes) of the single-workgroup launch of that kind (online_train_kernel / maml_train_kernel, kinds 1 and 2
+ * alike) at n_states; 0 where the kind does not serve that state count (kind 0, 1, 2: up to 128 states) or for another kind.
+ * The counterpart of mvn_lstm_train_lds_bytes: always within one CU's 163 840 bytes. */
+size_t mvn_vnet_train_lds_bytes(int32_t kind, int32_t n_states);
 
 /*
  * One block step of Trainer.eval_by_word (python_code/trainers/trainer.py:292-316 and the buffer entry of :322-324) for R

@@ -1030,8 +1030,8 @@ template <class Launch>  // launch(SC tag): picks the instantiation for S
 int dispatch_states(int S, bool many, Launch launch) {
     if (S == 16) return launch(std::integral_constant<int, 16>{});
     if (S == 32 && !many) return launch(std::integral_constant<int, 32>{});  // (R trials at S = 32 take the run-time form)
-    if (S == 64) return launch(std::integral_constant<int, 64>{});   // } online training only (launch_online_train)
-    if (S == 128) return launch(std::integral_constant<int, 128>{}); // }
+    if (S == 64) return launch(std::integral_constant<int, 64>{});   // } the single-workgroup forms of one trial (online_train_kernel,
+    if (S == 128) return launch(std::integral_constant<int, 128>{}); // } maml_train_kernel <64 | 128, false>)
     return launch(std::integral_constant<int, 0>{});
 }
 
@@ -1048,7 +1048,7 @@ int plan_online_groups(bool many, int R, int T, int M, int S, bool has_workspace
     return groups;
 }
 int plan_maml_groups(bool many, int R, int T, int W, int second_order, int S, bool has_workspace, size_t workspace_bytes) {
-    const int groups = maml_groups(T, W, second_order);  // one workgroup per chunk of the largest pass
+    const int groups = S > 32 ? 0 : maml_groups(T, W, second_order);  // one workgroup per chunk of the largest pass; 64 / 128 states: one workgroup
     const int cus = current_device_cus();
     if (groups < 2 || !has_workspace || sw(SW_TRAIN_GROUPS) == '0' || groups > cus) return 0;
     if (workspace_bytes < (many ? (size_t)R * trial_workspace_floats(S, groups) * sizeof(float) : maml_groups_workspace_bytes(S, groups)))
@@ -1144,14 +1144,15 @@ int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *man
     if (groups && (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
     if (!groups) {
         return dispatch_states(S, many != nullptr, [&](auto sc) -> int {
-            constexpr int SC = decltype(sc)::value > 32 ? 0 : decltype(sc)::value;  // (the meta-learning kernels: up to 32 states)
+            constexpr int SC1 = decltype(sc)::value;     // one trial: 64 / 128 states have their own form (maml_train.inc)
+            constexpr int SC = SC1 > 32 ? 0 : SC1;       // R trials: up to 32 states (the entry point refuses more)
             if (many) {
                 if (int e = ensure_dynamic_lds((const void *)maml_train_kernel<SC == 32 ? 0 : SC, true>, lds)) return e;
                 hipLaunchKernelGGL((maml_train_kernel<SC == 32 ? 0 : SC, true>), dim3(1, (unsigned)R), dim3(kTrainThreads), lds, st, one,
                                    many, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, lds_floats);
             } else {
-                if (int e = ensure_dynamic_lds((const void *)maml_train_kernel<SC, false>, lds)) return e;
-                hipLaunchKernelGGL((maml_train_kernel<SC, false>), dim3(1), dim3(kTrainThreads), lds, st, one, many, T, W, meta_lr,
+                if (int e = ensure_dynamic_lds((const void *)maml_train_kernel<SC1, false>, lds)) return e;
+                hipLaunchKernelGGL((maml_train_kernel<SC1, false>), dim3(1), dim3(kTrainThreads), lds, st, one, many, T, W, meta_lr,
                                    second_order, lr, beta1, beta2, eps, S, lds_floats);
             }
             return (int)hipGetLastError();
@@ -1169,7 +1170,7 @@ int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *man
                                 xcd ? groups : 0, nr, next_xcd_slot(xcd, many != nullptr)};
         const dim3 grid = xcd ? dim3(group_grid_blocks(groups, nr)) : dim3((unsigned)groups, (unsigned)nr);
         const int rc = dispatch_states(S, many != nullptr, [&](auto sc) -> int {
-            constexpr int SC = decltype(sc)::value > 32 ? 0 : decltype(sc)::value;  // (the meta-learning kernels: up to 32 states)
+            constexpr int SC = decltype(sc)::value > 32 ? 0 : decltype(sc)::value;  // (never above 32 states: plan_maml_groups)
             if (many) {
                 if (int e2 = ensure_dynamic_lds((const void *)maml_train_groups_kernel<SC == 32 ? 0 : SC, true>, lds)) return e2;
                 hipLaunchKernelGGL((maml_train_groups_kernel<SC == 32 ? 0 : SC, true>), grid,
@@ -1672,6 +1673,11 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
                                (hipStream_t)stream);
 }
 
+size_t mvn_vnet_train_lds_bytes(int32_t kind, int32_t S) {
+    if (kind < 0 || kind > 2 || !valid_states(S) || S > 128) return 0;
+    return kind == 0 ? online_train_lds_bytes(S) : maml_train_lds_floats(S) * sizeof(float);
+}
+
 int mvn_vnet_online_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t M, float lr, float beta1,
                                      float beta2, float eps, int32_t S, void *workspace, size_t workspace_bytes,
                                      mvn_stream_t stream) {
@@ -1700,7 +1706,8 @@ int mvn_vnet_maml_train_ws_f32(const float *rx_words, const int32_t *labels, int
                                void *workspace, size_t workspace_bytes, int32_t *status, mvn_stream_t stream) {
     // Adam only: the RMSprop / SGD tags (beta1 < 0) would turn lr / (1 - beta1^t) into an infinite or wrong step size
     if (T < 1 || W < 1 || n_steps < 0 || step0 < 0 || beta1 < 0.0f) return MVN_E_DIMS;
-    if (!valid_states(S) || S > 32) return MVN_E_STATES;  // four parameter-sized vectors + a chunk must fit the 160-KB LDS
+    // up to 32 states: four parameter-sized vectors + a chunk in the 160-KB LDS; 64 / 128: two vectors + a chunk (maml_train.inc)
+    if (!valid_states(S) || S > 128) return MVN_E_STATES;
     if (n_steps == 0) return MVN_OK;
     if (!rx_words || !labels || !support_idx || !query_idx || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !adam_m || !adam_v)
         return MVN_E_NULL;
@@ -1739,7 +1746,8 @@ int mvn_vnet_maml_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, i
 int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_W, int32_t S, size_t workspace_bytes, char *name,
                                int32_t name_len) {
     if (kind < 0 || kind > 2 || R < 0 || T < 1 || M_or_W < 0 || (kind > 0 && M_or_W < 1)) return MVN_E_DIMS;
-    if (!valid_states(S) || S > (kind == 0 ? 128 : 32)) return MVN_E_STATES;
+    // (the trial-batched meta-learning entry point stops at 32 states)
+    if (!valid_states(S) || S > 128 || (kind > 0 && R > 0 && S > 32)) return MVN_E_STATES;
     if (!name || name_len < 1) return MVN_E_NULL;
     const bool many = R > 0;
     const int n_trials = many ? R : 1;

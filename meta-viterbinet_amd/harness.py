@@ -368,13 +368,13 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
         buffer_tx, buffer_rx = [t.to(device=rx.device, dtype=torch.float32) for t in initial_buffer]
     meta_step = None  # meta.GraphedMetaStep, built at the first meta update (graphed_meta and a CUDA detector)
     graphed_meta = graphed_meta and rx.is_cuda and (online_trainer is None or online_trainer.optimizer_type == "Adam")  # captured Adam update
-    # mvn_vnet_maml_train_f32: the LDS holds 4 parameter vectors (n_states <= 32); the kernel's optimizer is Adam
+    # mvn_vnet_maml_train_f32: n_states <= 128 (4 parameter vectors in LDS up to 32 states, 2 at 64 / 128); the kernel's optimizer is Adam
     if lstm_meta:
         # every step of an update in ONE LSTMMetaTrainer.maml_training call, which takes the kernel (first order, one support word:
         # one launch) or autograd by its own meta_kernel_route; nothing is captured into a graph
         graphed_meta, hip_meta = False, True
     else:
-        hip_meta = (hip_meta and online_meta and rx.is_cuda and detector.n_states <= 32 and online_trainer is not None
+        hip_meta = (hip_meta and online_meta and rx.is_cuda and detector.n_states <= 128 and online_trainer is not None
                     and online_trainer.optimizer_type == "Adam" and online_trainer.use_kernel)
     support_idx = torch.arange(-window_size - 1, -1, device=rx.device).long()  # :288
     query_idx = -1 * torch.ones(1, device=rx.device).long()

@@ -214,8 +214,8 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     calling it yourself, no batching.  Banks at 4, 8, 32, 64 and 128 states take the lock-step engine with the running decision and
     with decision='path' (mvn_vnet_byword_step_states_f32 / mvn_vnet_byword_step_states_path_f32 for all R trials, words up to
     _lib.step_max_symbols(n_states) symbols, the run-time-n_states training kernels); what goes trial after trial through
-    harness.eval_by_word there: online_meta above 32 states (the meta-learning kernel's limit), longer words, and every other state
-    count.
+    harness.eval_by_word there: online_meta above 32 states (the trial-batched meta-learning kernel's limit; each trial's updates then
+    run on the one-trial kernel, maml_train_kernel<64 | 128, false>), longer words, and every other state count.
     cohorts > 1: the trials are split into that many groups that step ALTERNATELY on the same stream: while the GPU works
     through one group's training launches the host takes the decisions and fills the descriptors of the next (the host
     work of a step can only start after the step's sync).  Same launches per trial, same results.
@@ -319,7 +319,7 @@ def _lock_step_serves(n_states: int, rx: torch.Tensor, n_symbols: int, decision:
 def _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, initial_buffer, kw,
                          train_minibatch_size):
     """The trials of a bank the lock-step engine does not serve -- meta-learning with an optimizer its kernel does not implement
-    (RMSprop, SGD) or above 32 states, a state count or a decision without an R-word block step (_lock_step_serves) -- one after the
+    (RMSprop, SGD) or above the trial kernel's 32 states, a state count or a decision without an R-word block step (_lock_step_serves) -- one after the
     other through harness.eval_by_word; weights, saved weights, optimizer state and step counts go back into the bank."""
     from .detectors import META_VNETDetector, VNETDetector
     from .harness import eval_by_word
