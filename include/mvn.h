@@ -529,6 +529,26 @@ int mvn_va_montecarlo_f32(const double *h, int64_t Bh, double sigma, uint64_t se
                           int64_t *counters, int64_t B, int32_t T, int32_t L, int32_t S, mvn_stream_t stream);
 
 /*
+ * One uncoded Monte-Carlo point of the 16-state ViterbiNet, words generated inside the detector (vnet16_mc_kernel): the words of
+ * mvn_generate_words_f32 (same seed -> the same bits and samples, bit for bit) detected by the fused detector of
+ * mvn_vnet_decode_count_f32 and compared with the generated bits on the spot -- Trainer.single_eval_at_point,
+ * python_code/trainers/trainer.py:222-241, with no tx, y or decisions in memory.  counters[0..3] += {bit_errors, bits, frame_errors,
+ * frames}, exactly the counters of mvn_generate_words_f32 -> mvn_vnet_decode_count_f32(K = T) over the same words.
+ *   Words are addressed globally: the call runs n_rounds rounds of B words, round r on words word0 + r B .. word0 + (r + 1) B - 1 of
+ *   the generator's sequence (word w is row w of mvn_generate_words_f32 with any B > w), one launch per round, all enqueued on
+ *   `stream` without a synchronisation.  stop_frame_errors = F > 0: a round runs only if counters[2] < F held when the round before
+ *   it had completed (before the first one: with the counters as passed) -- a one-thread gate kernel between the rounds decides, so
+ *   a round runs whole or not at all and the same arguments give the same integers every time.  F = 0 runs every round.
+ *   h [Bh,L] float64 taps (row w % Bh for word w), sigma = 10^(-snr/20); W1..b3: ViterbiNet's six arrays as in mvn_vnet_decode_f32;
+ *   counters: device int64[4], accumulated into; progress: device int32[2] that the caller has ZEROED, {rounds that ran, gate flag},
+ *   required when n_rounds > 1 or F > 0 and otherwise optional (NULL with n_rounds = 1, F = 0: exactly one launch).
+ *   S = 16, L = 4 (MVN_E_STATES for any other S: run mvn_generate_words_f32 + mvn_vnet_decode_count_f32 there); T > 0.
+ */
+int mvn_vnet_montecarlo_f32(const double *h, int64_t Bh, double sigma, uint64_t seed, int64_t word0, const float *W1, const float *b1,
+                            const float *W2, const float *b2, const float *W3, const float *b3, int64_t *counters, int32_t *progress,
+                            int64_t B, int32_t n_rounds, int64_t stop_frame_errors, int32_t T, int32_t L, int32_t S, mvn_stream_t stream);
+
+/*
  * Reed-Solomon outer code, batched over words; bits are fp32 {0,1}, 8 per GF(2^8)
  * symbol, MSB first (np.packbits).  Same code and same behaviour past the correction capacity as
  * python_code/ecc/rs_main.py: encode (:9-18) / decode (:21-37) -- prim 0x11d, generator 2, nsym parity bytes,

@@ -476,6 +476,7 @@ int ensure_dynamic_lds(const void *fn, size_t bytes);  // raises a kernel's dyna
 #include "train_groups.inc"
 #include "word_gen.inc"
 #include "va_montecarlo.inc"
+#include "vnet_montecarlo.inc"
 
 // -------------------------------------------------------------------------------------------
 // metrics.py:7-17 as integer counters.  One wave per row, block-level reduction, one atomic
@@ -1920,6 +1921,18 @@ int mvn_va_montecarlo_f32(const double *h, int64_t Bh, double sigma, uint64_t se
     if (B == 0 || T == 0) return MVN_OK;
     if (!h || !state_priors) return MVN_E_NULL;
     return launch_va_montecarlo(h, Bh, sigma, seed, state_priors, Bp, (unsigned long long *)counters, B, T, L, S, (hipStream_t)stream);
+}
+
+int mvn_vnet_montecarlo_f32(const double *h, int64_t Bh, double sigma, uint64_t seed, int64_t word0, const float *W1, const float *b1,
+                            const float *W2, const float *b2, const float *W3, const float *b3, int64_t *counters, int32_t *progress,
+                            int64_t B, int32_t n_rounds, int64_t stop_frame_errors, int32_t T, int32_t L, int32_t S, mvn_stream_t stream) {
+    if (S != 16) return MVN_E_STATES;  // the fused ViterbiNet kernels are the 16-state ones: generate + decode + count elsewhere
+    if (L < 0 || L > 16 || S != (1 << L) || T <= 0 || B < 0 || n_rounds < 0 || Bh <= 0 || word0 < 0 || stop_frame_errors < 0) return MVN_E_DIMS;
+    if (B == 0 || n_rounds == 0) return MVN_OK;
+    if (!h || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !counters) return MVN_E_NULL;
+    if (!progress && (n_rounds > 1 || stop_frame_errors > 0)) return MVN_E_NULL;
+    return launch_vnet_montecarlo(h, Bh, sigma, seed, word0, W1, b1, W2, b2, W3, b3, (unsigned long long *)counters, progress, B, n_rounds,
+                                  stop_frame_errors, T, (hipStream_t)stream);
 }
 
 int mvn_rs_decode_bits_f32(const float *rx_bits, int64_t ld_in, float *msg_bits, int64_t ld_out, int32_t *status,

@@ -86,6 +86,56 @@ def va_monte_carlo(detector, n_words: int, snr: float, gamma: float, device, see
     return counters
 
 
+def vnet_monte_carlo(detector, n_words: int, h, snr: float, device, seed: int, counters: Optional[torch.Tensor] = None,
+                     first_word: int = 0, rounds: int = 1, stop_frame_errors: int = 0):
+    """One uncoded Monte-Carlo point of the 16-state ViterbiNet with the words generated INSIDE the detector
+    (mvn_vnet_montecarlo_f32): Trainer.single_eval_at_point (trainer.py:222-241) with no tx, y or decisions in device memory.
+    `detector`: a 16-state VNETDetector (its weights are read at call time); T = detector.transmission_lengths['val'], L = 4.
+    `h`: estimate_channel(...) rows [Bh, 4] (ViterbiNet carries no channel of its own; an array, or a float64 tensor already on
+    `device`); word w uses row w % Bh.
+    Returns the int64[4] counters {bit_errors, bits, frame_errors, frames} on `device` (accumulated into `counters` when given): the
+    same numbers as detector.val_count(y, tx) over rows first_word : first_word + n_words of
+    (tx, y) = generate_words(first_word + n_words, T, h, snr, 4, device, seed).
+
+    rounds = R > 1 runs R rounds of n_words words each (round r: words first_word + r n_words ...), all enqueued at once;
+    stop_frame_errors = F > 0 lets a round run only if fewer than F frame errors had been counted when the round before it
+    completed -- the run-to-F-frame-errors form of a BER/FER point, decided on the device between the rounds: the call never
+    synchronises, a round runs whole or not at all, and the same arguments give the same integers every time.  With rounds > 1
+    the call returns (counters, rounds_run), rounds_run an int32 device tensor (read it when the counters are read).
+
+    Sharding a point over ranks: words are addressed globally, so rank r of `world` calls
+    lo, hi = shard_range(n_total, r, world); vnet_monte_carlo(det, hi - lo, h, snr, device, seed, first_word=lo) and the ranks
+    all_reduce(SUM) the counters as sharded_eval does -- 1, 2, 4 or 8 ranks give identical integers.  (With rounds, a rank's round r
+    starts at first_word + r n_words: give every rank its own contiguous range of rounds * n_words words.)"""
+    from . import _lib
+
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.MvnError("vnet_monte_carlo runs on an MI355X (ROCm) device only")
+    S, L = detector.n_states, 4
+    T = detector.transmission_lengths["val"]
+    if n_words < 0 or rounds < 0 or first_word < 0 or stop_frame_errors < 0:
+        raise ValueError("n_words, rounds, first_word and stop_frame_errors must not be negative")
+    from .detectors import _weights_on
+
+    if torch.is_tensor(h):
+        hd = h.to(device=dev, dtype=torch.float64).reshape(-1, L).contiguous()
+    else:
+        hd = torch.as_tensor(np.ascontiguousarray(h, dtype=np.float64).reshape(-1, L), device=dev)
+    w = _weights_on(detector._params(), dev, S)  # read at call time, never cached
+    if counters is None:
+        counters = torch.zeros(4, dtype=torch.int64, device=dev)
+    staged = rounds > 1 or stop_frame_errors > 0
+    progress = torch.zeros(2, dtype=torch.int32, device=dev) if staged else None
+    sigma = (10 ** (snr / 10)) ** (-0.5)  # channel.py:23,31
+    with torch.cuda.device(dev):
+        rc = _lib.load().mvn_vnet_montecarlo_f32(_lib.ptr(hd), hd.shape[0], float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, first_word,
+                                                 *[_lib.ptr(t) for t in w], _lib.ptr(counters), _lib.ptr(progress), n_words, rounds,
+                                                 stop_frame_errors, T, L, S, _lib.current_stream(dev))
+    _lib.check(rc, "mvn_vnet_montecarlo_f32")
+    return (counters, progress[0]) if rounds > 1 else counters
+
+
 def _gpu_counter(detected: torch.Tensor, tx: torch.Tensor, rows: Optional[torch.Tensor]) -> torch.Tensor:
     return _metrics.count_errors(detected, tx, rows)
 
