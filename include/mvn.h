@@ -295,6 +295,9 @@ int mvn_vnet_maml_train_ws_f32(const float *rx_words, const int32_t *labels, int
  * trial's workgroups only ever synchronise with each other (per-trial barrier counter in the workspace), trials with n = 0
  * exit at once, and a launch never holds more workgroups than the device has CUs (more trials = more launches on `stream`).
  * Per trial the results are bit-identical to the single-trial entry points.
+ * State counts: mvn_vnet_online_train_trials_f32 serves S <= 128, mvn_vnet_maml_train_trials_f32 S <= 32; the meta-learning step
+ * at S = 64 and 128 has a trial-batched entry point of its own, mvn_vnet_maml_train_states_trials_f32 (below: one workgroup per
+ * trial, no workspace, any number of trials in one launch, and an aliasing contract for the descriptors' weight arrays).
  */
 typedef struct mvn_train_trial {
     const float *y;           /* online: the word [T]; maml: the buffered received words [Nw, T] */
@@ -322,6 +325,29 @@ int mvn_vnet_online_train_trials_f32(const mvn_train_trial_t *trials, int32_t R,
 int mvn_vnet_maml_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t W, float meta_lr,
                                    int32_t second_order, float lr, float beta1, float beta2, float eps, int32_t S,
                                    void *workspace, size_t workspace_bytes, mvn_stream_t stream);
+
+/*
+ * The trial axis of the meta-learning step at S = 64 and 128 (mvn_vnet_maml_train_trials_f32 serves S <= 32 and returns
+ * MVN_E_STATES above): maml_train_states_trials_kernel<64 | 128>, grid (1, R), trial r = trials[r] of the DEVICE array, one
+ * workgroup per trial running the very body of the one-trial call.  Per trial the results are bit-identical to
+ * mvn_vnet_maml_train_ws_f32 run alone.  No workspace: this form has no barrier between workgroups, so the trials of a launch
+ * never wait for each other, no residency condition applies and ANY R (up to 65535) runs in ONE launch -- R above the CU count
+ * simply takes ceil(R / CUs) rounds of workgroups.  A trial with n = 0 exits at once and touches nothing.
+ * The aliasing contract (the LDS holds two parameter-sized vectors, so between the two gradient passes of every step the
+ * weights wait in the trial's w_out arrays, which hold intermediate values while the launch runs):
+ *   - a trial's w_out, w_out2, adam_m and adam_v must not overlap any array of ANOTHER trial of the launch, nor a w_in row that
+ *     another trial reads (a row shared by several trials is read-only for the whole launch);
+ *   - w_in is read once, before the trial's first step, and never again: it may equal the trial's own w_out (training in place)
+ *     or its own w_out2 (restart from the saved detector, which is rewritten only when the trial ends), or be a row all trials
+ *     share (weights_init = 'meta_training');
+ *   - w_out and w_out2 of one trial must differ (w_out2 all NULL: no second copy).
+ * status is never written by this call (nothing in it can give up) and loss_out may be NULL.
+ * Returns, in this order: MVN_E_DIMS (T < 1, W < 1, R < 0 or > 65535, beta1 < 0: Adam only), MVN_E_STATES (S not 64 or 128),
+ * MVN_OK for R == 0, MVN_E_NULL (trials == NULL), else the launch's result.
+ */
+int mvn_vnet_maml_train_states_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t W, float meta_lr,
+                                          int32_t second_order, float lr, float beta1, float beta2, float eps, int32_t S,
+                                          mvn_stream_t stream);
 
 /*
  * Introspection for tests and profiling tools (no reference counterpart): which device kernel, in which form, a training

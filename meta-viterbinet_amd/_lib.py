@@ -60,6 +60,8 @@ SIGNATURES = {
     "mvn_vnet_online_train_trials_f32": (ctypes.c_int, [_vp, _i32, _i32, _i32] + [ctypes.c_float] * 4 + [_i32, _vp, ctypes.c_size_t, _vp]),
     "mvn_vnet_maml_train_trials_f32": (ctypes.c_int, [_vp, _i32, _i32, _i32, ctypes.c_float, _i32] + [ctypes.c_float] * 4 +
                                        [_i32, _vp, ctypes.c_size_t, _vp]),
+    "mvn_vnet_maml_train_states_trials_f32": (ctypes.c_int, [_vp, _i32, _i32, _i32, ctypes.c_float, _i32] + [ctypes.c_float] * 4 +
+                                              [_i32, _vp]),
     "mvn_vnet_train_kernel_name": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.c_size_t, ctypes.c_char_p, _i32]),
     "mvn_vnet_train_lds_bytes": (ctypes.c_size_t, [_i32, _i32]),
     "mvn_vnet_byword_step_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),

@@ -824,6 +824,27 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_kernel<128, false>(
     maml_train_states<128>(one, T, W, meta_lr, second_order, lr, beta1, beta2, eps, lds_floats);
 }
 
+// ---- R trials at 64 and 128 states: maml_train_states_trials_kernel<64 | 128>, grid (1, R) ----------------------------------
+// The same body, the trial being many[blockIdx.y] of a device array (mvn_vnet_maml_train_states_trials_f32).  The step needs no
+// workspace and has no barrier between workgroups, so one workgroup IS one trial and the trials of a launch never wait for each
+// other: no residency condition applies, R above the CU count runs in ONE launch with gridDim.y = R (a workgroup fills a CU's LDS,
+// the dispatcher starts the next trial where one ends).  A trial with n = 0 exits at once and touches nothing.
+// What the body asks of the descriptors (include/mvn.h has the contract):
+//   * theta waits in d.w_out between the two gradient passes of every step (store_params before the inner step, load_params
+//     after the query pass), so w_out holds intermediate values while the launch runs and must belong to this trial alone;
+//   * d.w_in is read once, by the load_params before the first step, and never again: it may be the trial's own w_out or
+//     w_out2 (the saved row, written only by store_trial_params at the end) or a row all trials share read-only;
+//   * `status` is never written (nothing here can give up); loss_out may be NULL.
+// The descriptor is a reference into global memory instead of a kernel argument; blockIdx.y is uniform, so its pointers and
+// n / b1pow / b2pow arrive by scalar loads as the by-value form's do from the kernel-argument segment.
+template <int SC>
+__global__ __launch_bounds__(kTrainThreads) void maml_train_states_trials_kernel(
+    const mvn_train_trial_t *__restrict__ many, int T, int W, float meta_lr, int second_order, float lr, float beta1, float beta2,
+    float eps, int lds_floats) {
+    static_assert(SC == 64 || SC == 128, "64 or 128 states (up to 32: maml_train_kernel<SC, true>)");
+    maml_train_states<SC>(many[blockIdx.y], T, W, meta_lr, second_order, lr, beta1, beta2, eps, lds_floats);
+}
+
 // floats of one parameter vector in LDS (train_layout's P4)
 constexpr int train_p4(int S) { return (2 * kH1 + kH2 * kH1Ld + kH2 + S * kH2 + S + 3) & ~3; }
 constexpr size_t maml_train_lds_floats(int S) {

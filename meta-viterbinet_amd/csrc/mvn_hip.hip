@@ -1189,6 +1189,22 @@ int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *man
     return MVN_OK;
 }
 
+// R trials at 64 / 128 states: one workgroup per trial, all of them in ONE launch whatever R is (no workspace, no barrier
+// between workgroups, hence nothing that has to be resident together; maml_train.inc)
+int launch_maml_train_states_trials(const mvn_train_trial_t *many, int R, int T, int W, float meta_lr, int second_order, float lr,
+                                    float beta1, float beta2, float eps, int S, hipStream_t st) {
+    const size_t lds = maml_train_lds_floats(S) * sizeof(float);
+    const int lds_floats = (int)maml_train_lds_floats(S);
+    auto launch = [&](auto sc) -> int {
+        constexpr int SC = decltype(sc)::value;
+        if (int e = ensure_dynamic_lds((const void *)maml_train_states_trials_kernel<SC>, lds)) return e;
+        hipLaunchKernelGGL((maml_train_states_trials_kernel<SC>), dim3(1, (unsigned)R), dim3(kTrainThreads), lds, st, many, T, W,
+                           meta_lr, second_order, lr, beta1, beta2, eps, lds_floats);
+        return (int)hipGetLastError();
+    };
+    return S == 64 ? launch(std::integral_constant<int, 64>{}) : launch(std::integral_constant<int, 128>{});
+}
+
 #include "lstm.inc"
 #include "lstm_train.inc"
 
@@ -1742,6 +1758,17 @@ int mvn_vnet_maml_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, i
     if (!trials) return MVN_E_NULL;
     return launch_maml_train(mvn_train_trial_t{}, trials, R, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, workspace,
                              workspace_bytes, (hipStream_t)stream);
+}
+
+int mvn_vnet_maml_train_states_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t W, float meta_lr,
+                                          int32_t second_order, float lr, float beta1, float beta2, float eps, int32_t S,
+                                          mvn_stream_t stream) {
+    // (Adam only, as above; R is gridDim.y of the one launch)
+    if (T < 1 || W < 1 || R < 0 || R > 65535 || beta1 < 0.0f) return MVN_E_DIMS;
+    if (S != 64 && S != 128) return MVN_E_STATES;  // up to 32 states: mvn_vnet_maml_train_trials_f32
+    if (R == 0) return MVN_OK;
+    if (!trials) return MVN_E_NULL;
+    return launch_maml_train_states_trials(trials, R, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, (hipStream_t)stream);
 }
 
 int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_W, int32_t S, size_t workspace_bytes, char *name,

@@ -10,7 +10,8 @@ MI355X's 256 CUs; here R trials step through their blocks together:
                      ONE device-to-host copy of the R error counts (the only sync: every trial's next move depends on its
                      coded ser, trainer.py:305,319)  ->  per-trial decisions on the
                      host  ->  at most ONE mvn_vnet_maml_train_trials_f32 and ONE mvn_vnet_online_train_trials_f32 launch
-                     sequence for the trials that train (gridDim.y = trial, per-trial barrier counters).
+                     sequence for the trials that train (gridDim.y = trial, per-trial barrier counters); at 64 and 128
+                     states the meta-learning launch is mvn_vnet_maml_train_states_trials_f32 (a workgroup per trial).
 
 All per-trial state lives in stacked device tensors (TrialBank); the reference's buffer of (received word, label word) pairs
 is a list of block numbers per trial (the words themselves stay where the step kernel wrote them).  Per trial, the results --
@@ -197,7 +198,8 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
                          window_size: int = 1, meta_train_iterations: int = 20, meta_j_num: int = 10, meta_subframes: int = 5,
                          meta_style_online_training: bool = False, train_minibatch_size: int = 32,
                          weights_init: str = "last_frame", meta_training_weights=None, record: Optional[dict] = None,
-                         cohorts: int = 1, initial_buffer=None, decision: str = "running", list_bytes: Optional[int] = None) -> np.ndarray:
+                         cohorts: int = 1, initial_buffer=None, decision: str = "running", list_bytes: Optional[int] = None,
+                         meta_trial_axis: Optional[bool] = None) -> np.ndarray:
     """R trials of harness.eval_by_word (= Trainer.eval_by_word, trainer.py:267-354) at once, with the reference's switches:
     buffer_empty True / False, weights_init last_frame / random / meta_training, Adam / RMSprop / SGD.
     tx [R, N, K] message bits, rx [R, N, K + 8 n_symbols] received words (trial r = row r, its own SNR / channel / seed);
@@ -214,8 +216,15 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     calling it yourself, no batching.  Banks at 4, 8, 32, 64 and 128 states take the lock-step engine with the running decision and
     with decision='path' (mvn_vnet_byword_step_states_f32 / mvn_vnet_byword_step_states_path_f32 for all R trials, words up to
     _lib.step_max_symbols(n_states) symbols, the run-time-n_states training kernels); what goes trial after trial through
-    harness.eval_by_word there: online_meta above 32 states (the trial-batched meta-learning kernel's limit; each trial's updates then
-    run on the one-trial kernel, maml_train_kernel<64 | 128, false>), longer words, and every other state count.
+    harness.eval_by_word there: longer words, every other state count, and online_meta at 64 / 128 states with ONE trial (below).
+    online_meta at 64 and 128 states (_meta_states_serves): the meta-learning updates of all trials run in one
+    mvn_vnet_maml_train_states_trials_f32 launch (maml_train_states_trials_kernel<64 | 128>, a workgroup per trial, no workspace),
+    everything else as at the other state counts.  meta_trial_axis chooses that route: None (default) takes it when it serves the
+    bank and R >= META_TRIAL_AXIS_MIN_R = 2 -- one trial has nothing to batch and goes through harness.eval_by_word, whose updates
+    run on the one-trial kernel maml_train_kernel<64 | 128, false>; True takes it whenever it serves the bank, R = 1 included;
+    False never takes it (every trial through harness.eval_by_word, one after the other).  Same rows either way.  The keyword
+    changes nothing where the route does not apply: up to 32 states, 256 states, RMSprop / SGD with online_meta, decision='list',
+    longer words, no online_meta; an LSTM bank accepts and ignores it.
     cohorts > 1: the trials are split into that many groups that step ALTERNATELY on the same stream: while the GPU works
     through one group's training launches the host takes the decisions and fills the descriptors of the next (the host
     work of a step can only start after the step's sync).  Same launches per trial, same results.
@@ -239,6 +248,9 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
 
     if decision not in ("running", "path", "list"):
         raise ValueError(f"decision must be 'running', 'path' or 'list', got {decision!r}")
+    if meta_trial_axis is not None and not isinstance(meta_trial_axis, (bool, np.bool_)):
+        raise ValueError(f"meta_trial_axis must be None, True or False, got {meta_trial_axis!r}")
+    meta_trial_axis = None if meta_trial_axis is None else bool(meta_trial_axis)
     if decision in ("path", "list") and isinstance(bank, LSTMTrialBank):
         raise ValueError(f"decision={decision!r} needs a Viterbi / ViterbiNet detector (an LSTM detector has no trellis to trace back)")
     if decision == "list":
@@ -273,7 +285,10 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
                                         ser_thresh, online_meta, meta_lr, MAML, window_size, meta_train_iterations, meta_j_num,
                                         meta_subframes, meta_style_online_training, weights_init, meta_training_weights, record,
                                         initial_buffer)
-    if (bank.optimizer_type != "Adam" and online_meta) or not _lock_step_serves(bank.n_states, rx, n_symbols, decision, online_meta):
+    meta_states = (meta_trial_axis is not False and (meta_trial_axis or R >= META_TRIAL_AXIS_MIN_R)
+                   and _meta_states_serves(bank.n_states, rx, n_symbols, decision, online_meta, bank.optimizer_type))
+    if (bank.optimizer_type != "Adam" and online_meta) or not (
+            meta_states or _lock_step_serves(bank.n_states, rx, n_symbols, decision, online_meta)):
         return _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, initial_buffer,
                                     dict(self_supervised=self_supervised, self_supervised_iterations=self_supervised_iterations,
                                          ser_thresh=ser_thresh, online_meta=online_meta, meta_lr=meta_lr, MAML=MAML, window_size=window_size,
@@ -316,10 +331,28 @@ def _lock_step_serves(n_states: int, rx: torch.Tensor, n_symbols: int, decision:
             and T // 8 > n_symbols and T <= _lib.step_max_symbols(n_states) and not (online_meta and n_states > 32))
 
 
+# mvn_vnet_maml_train_states_trials_f32: the state counts of maml_train_states_trials_kernel, and the fewest trials for which
+# eval_by_word_batched takes that route by default (one trial has nothing to batch; DESIGN 5.5 has the measurement behind it)
+META_STATES = (64, 128)
+META_TRIAL_AXIS_MIN_R = 2
+
+
+def _meta_states_serves(n_states: int, rx: torch.Tensor, n_symbols: int, decision: str, online_meta: bool,
+                        optimizer_type: str = "Adam") -> bool:
+    """Whether the lock-step engine serves this bank WITH online meta-learning at 64 / 128 states, where _lock_step_serves says no:
+    the meta-learning updates then run on mvn_vnet_maml_train_states_trials_f32 (Adam only, like every meta-learning kernel), the
+    block step is the running or the path step (not 'list') under the word conditions of _lock_step_serves."""
+    T = rx.shape[2]
+    return (n_states in META_STATES and bool(online_meta) and optimizer_type == "Adam" and decision in ("running", "path")
+            and n_states in _lib.STEP_STATES and rx.is_cuda and T % 8 == 0 and 1 <= n_symbols <= 8 and T // 8 > n_symbols
+            and T <= _lib.step_max_symbols(n_states))
+
+
 def _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, initial_buffer, kw,
                          train_minibatch_size):
-    """The trials of a bank the lock-step engine does not serve -- meta-learning with an optimizer its kernel does not implement
-    (RMSprop, SGD) or above the trial kernel's 32 states, a state count or a decision without an R-word block step (_lock_step_serves) -- one after the
+    """The trials of a bank the lock-step engine does not serve -- meta-learning with an optimizer its kernels do not implement
+    (RMSprop, SGD), at 64 / 128 states with a single trial or meta_trial_axis=False (_meta_states_serves and eval_by_word_batched),
+    a state count or a decision without an R-word block step (_lock_step_serves) -- one after the
     other through harness.eval_by_word; weights, saved weights, optimizer state and step counts go back into the bank."""
     from .detectors import META_VNETDetector, VNETDetector
     from .harness import eval_by_word
@@ -489,9 +522,14 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
                 bank.step[a] += ns
                 idx.send(4 * pos)
                 desc.send(len(act) * TRIAL_DTYPE.itemsize)
-                rc = lib.mvn_vnet_maml_train_trials_f32(desc_meta_ptr, len(act), T, W, meta_lr, 1 if MAML else 0, bank.lr,
-                                                        b1, b2, bank.eps, S, _lib.ptr(ws), ws_bytes, stream)
-                _lib.check(rc, "mvn_vnet_maml_train_trials_f32")
+                if S in META_STATES:  # a workgroup per trial, no workspace (ws_bytes is 0 there)
+                    rc = lib.mvn_vnet_maml_train_states_trials_f32(desc_meta_ptr, len(act), T, W, meta_lr, 1 if MAML else 0, bank.lr,
+                                                                   b1, b2, bank.eps, S, stream)
+                    _lib.check(rc, "mvn_vnet_maml_train_states_trials_f32")
+                else:
+                    rc = lib.mvn_vnet_maml_train_trials_f32(desc_meta_ptr, len(act), T, W, meta_lr, 1 if MAML else 0, bank.lr,
+                                                            b1, b2, bank.eps, S, _lib.ptr(ws), ws_bytes, stream)
+                    _lib.check(rc, "mvn_vnet_maml_train_trials_f32")
         # ---- self-supervised training on the word just buffered (trainer.py:345-347)
         if self_supervised and push.any():
             act = np.flatnonzero(push)
