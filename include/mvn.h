@@ -537,6 +537,17 @@ int mvn_isi_awgn_transmit(const float *bits, int64_t ld_bits, int32_t K, const v
  * reference's two RandomState streams, not the same stream -- mvn_isi_awgn_transmit replays recorded draws bit for bit).
  *   tx [B, tx_ld>=T] transmitted bits as fp32 {0.,1.} (NULL: not stored); y [B, y_ld>=T] received words;
  *   h [Bh,L] float64 taps (row b % Bh for word b), sigma = 10^(-snr/20) (channel.py:23,31); L <= 16.
+ * The function of (seed, b, t), b = b_lo + 2^32 b_hi the word and key = (seed low half, seed high half):
+ *   bit c[b,t]   = bit (t % 128) of philox(key, counter (t / 128, b_lo, b_hi, 0)), least-significant bit of the first word first;
+ *   noise z[b,t] : (x, y, z, w) = philox(key, counter (t / 4, b_lo, b_hi, 1)); for (a, b') = (x, y) [(z, w)], in float32,
+ *                  u1 = 2^-31 ((a >> 1) + 0.5) in [2^-32, 1], u2 = 2^-32 b' in [0, 1], r = sqrt(-2 ln u1) <= sqrt(64 ln 2) ~ 6.67;
+ *                  samples 4 (t / 4) + {0, 1} [{2, 3}] = r cos(2 pi u2), r sin(2 pi u2);
+ *   y[b,t]       = fp32( sum_{k=0..L-1} h[b % Bh][L-1-k] (1 - 2 c[b,t+k]) + sigma z[b,t] ), c = 0 from T on, the sum and the
+ *                  product in float64 in this order.
+ * Nothing else enters: not B, not the tx / y layout, not h or sigma in z -- rows 0 .. B-1 of a call are the first rows of any larger
+ * call, and mvn_vnet_montecarlo_f32 below addresses the same sequence from any word0 on.  tests/word_gen_ref.py is this
+ * definition in NumPy; the bits and the float64 sum are reproduced bit for bit, z to the float32 accuracy of logf, sqrtf and the
+ * hardware sine / cosine (a measured relative error of r: profiles/word_gen_exactness.txt).
  */
 int mvn_generate_words_f32(float *tx, int64_t tx_ld, float *y, int64_t y_ld, const double *h, int64_t Bh, double sigma,
                            uint64_t seed, int64_t B, int32_t T, int32_t L, mvn_stream_t stream);

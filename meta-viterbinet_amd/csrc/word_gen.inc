@@ -11,7 +11,13 @@
 //   bits  : word b, 128-bit group g = t / 128 -> philox(key = seed, counter = (g, b_lo, b_hi, 0)), bit (t % 128),
 //           least-significant bit of the .x word first
 //   noise : standard normal by Box-Muller on two 32-bit uniforms, 4 samples per philox(key = seed, counter =
-//           (t / 4, b_lo, b_hi, 1)); |z| <= 6.8 sigma (u1 >= 2^-33)
+//           (t / 4, b_lo, b_hi, 1)) = (x, y, z, w): samples 4q, 4q + 1 = r cos, r sin from (x, y), 4q + 2, 4q + 3 from (z, w).
+//           The uniforms are float32 and their ends are reached: u1 = 2^-31 (a/2 + 1/2) lies in [2^-32, 1] ((float)(a >> 1) rounds
+//           up to 2^31 from a >> 1 = 2^31 - 64 on, and the + 0.5 is absorbed from 2^23 on), u2 = 2^-32 b lies in [0, 1] ((float)b
+//           rounds up to 2^32).  So |z| <= sqrt(-2 ln 2^-32) = sqrt(64 ln 2) ~ 6.67, and z = 0 for the pair when u1 rounds to 1
+//           (probability 2^-25); u2 = 1 is the angle 0 again.  Neither end is harmful.
+//   tests/word_gen_ref.py restates all of this in NumPy and tests/test_gpu_word_gen.py holds the kernel to it: bits and ISI sum bit
+//   for bit, the noise sample to a measured relative error of r (profiles/word_gen_exactness.txt), their composition bit for bit.
 //   y[t]  = sum_k h[L-1-k] * s[t+k] + sigma * z, s = 1 - 2 c, c = 0 beyond the word (channel_dataset.py:71): float64
 //           accumulation like the reference's NumPy code, stored fp32 (channel_dataset.py:103).
 
@@ -36,8 +42,8 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 }
 
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float &z0, float &z1) {
-    const float u1 = ((float)(a >> 1) + 0.5f) * 4.656612873077392578125e-10f;  // (0, 1): 2^-31 * (a/2 + 1/2)
-    const float u2 = (float)b * 2.3283064365386962890625e-10f;                   // [0, 1)
+    const float u1 = ((float)(a >> 1) + 0.5f) * 4.656612873077392578125e-10f;  // [2^-32, 1]: 2^-31 * (a/2 + 1/2), rounded
+    const float u2 = (float)b * 2.3283064365386962890625e-10f;                   // [0, 1]: (float)b rounds up to 2^32
     const float r = sqrtf(-2.0f * logf(u1));
     z0 = r * __builtin_amdgcn_cosf(u2);  // v_cos_f32 / v_sin_f32 take their argument in revolutions: cos(2 pi u2)
     z1 = r * __builtin_amdgcn_sinf(u2);

@@ -95,6 +95,23 @@ def test_argument_validation_needs_no_device(lib):
     assert lib.mvn_vnet_train_trials_workspace_bytes(64, 136, 1, 4) == 0
 
 
+def test_generate_words_validates_before_touching_a_device(lib):
+    """mvn_generate_words_f32: 1 <= L <= 16, rows at least T apart (tx only when it is stored), at least one tap row; empty calls do
+    nothing; then the pointers."""
+    p = ctypes.c_void_p(256)  # never dereferenced: every call below returns before a launch
+    gen = lambda tx, tx_ld, y, y_ld, h, Bh, B, T, L: lib.mvn_generate_words_f32(tx, tx_ld, y, y_ld, h, Bh, 0.5, 7, B, T, L, None)  # noqa: E731
+    assert gen(p, 8, p, 8, p, 1, 4, 8, 0) == -1 and gen(p, 8, p, 8, p, 1, 4, 8, 17) == -1 and gen(p, 8, p, 8, p, 1, 4, 8, -1) == -1
+    assert gen(p, 8, p, 7, p, 1, 4, 8, 4) == -1  # y_ld < T
+    assert gen(p, 7, p, 8, p, 1, 4, 8, 4) == -1  # tx_ld < T with tx stored
+    assert gen(None, 0, None, 8, p, 1, 4, 8, 4) == -4  # (tx_ld is not looked at without tx: the NULL y is what is wrong)
+    assert gen(p, 8, p, 8, p, 0, 4, 8, 4) == -1 and gen(p, 8, p, 8, p, -1, 4, 8, 4) == -1  # Bh
+    assert gen(p, 8, p, 8, p, 1, -1, 8, 4) == -1 and gen(p, 8, p, 8, p, 1, 4, -1, 4) == -1
+    assert gen(None, 8, None, 8, None, 1, 0, 8, 4) == 0 and gen(None, 0, None, 0, None, 1, 4, 0, 4) == 0  # B = 0, T = 0
+    assert gen(p, 8, None, 8, p, 1, 4, 8, 4) == -4 and gen(p, 8, p, 8, None, 1, 4, 8, 4) == -4
+    for L in (1, 16):  # the ends of the range pass the shape checks
+        assert gen(None, 8, None, 8, None, 1, 4, 8, L) == -4
+
+
 def test_test_hooks_are_not_in_the_shipped_library(lib):
     """mvn_test_hooks (forces the training kernels' barrier to give up) exists in the tests' -DMVN_TEST_HOOKS build only."""
     import meta_viterbinet_amd as mvn

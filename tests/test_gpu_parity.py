@@ -10,10 +10,11 @@ import pytest
 import torch
 
 import meta_viterbinet_amd as mvn
+from word_gen_ref import philox4x32_10 as _philox4x32_10
 
 pytestmark = pytest.mark.gpu
 
-CC = {"train": "time_decay", "val": "time_decay"}
+CC ={"train": "time_decay", "val": "time_decay"}
 
 
 @pytest.fixture(scope="module")
@@ -2070,23 +2071,15 @@ def test_config4_meta_viterbinet_reference_defaults(golden, dev):
 
 
 # ---------------------------------------------------------------- f#1: fused on-device word generator
-def _philox4x32_10(c, k):
-    """NumPy Philox4x32-10 (Salmon et al. 2011; Random123): c [n,4] uint32 counters, k (k0, k1) -> [n,4] uint32."""
-    c = c.astype(np.uint64)
-    k0, k1 = np.uint64(k[0]), np.uint64(k[1])
-    M0, M1, MASK = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = M0 * c[:, 0], M1 * c[:, 2]
-        c = np.stack([(p1 >> np.uint64(32)) ^ c[:, 1] ^ k0, p1 & MASK, (p0 >> np.uint64(32)) ^ c[:, 3] ^ k1, p0 & MASK], axis=1)
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & MASK, (k1 + np.uint64(0xBB67AE85)) & MASK
-    return c.astype(np.uint32)
+# (_philox4x32_10: the NumPy restatement in word_gen_ref.py, which test_gpu_word_gen.py builds the generator's referee on)
 
 
 def test_word_generator_bits_are_philox_and_noise_is_standard_normal(dev):
     """mvn_generate_words_f32 (channel_dataset.py:65-83 + channel.py:12-35 in one kernel).  Integer part bit-exact: the
     transmitted bits are Philox4x32-10 output (NumPy restatement checked against the Random123 known answers).  The
     received words equal the replay kernel's noise-free output plus sigma * z with z ~ N(0,1): Kolmogorov-Smirnov against
-    the normal CDF, moments, and no correlation with the neighbour sample or the bits."""
+    the normal CDF, moments, and no correlation with the neighbour sample or the bits.  These are the statistics; every sample's
+    value -- bits, ISI sum, noise and their composition -- is held to the NumPy restatement in tests/test_gpu_word_gen.py."""
     import scipy.stats
 
     kat = _philox4x32_10(np.array([[0, 0, 0, 0], [0xFFFFFFFF] * 4, [0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344]], np.uint32), (0, 0))
