@@ -52,7 +52,7 @@ typedef void *mvn_stream_t; /* hipStream_t */
 
 #define MVN_E_BARRIER (-7)   /* (status words only) a training launch abandoned its device-wide barrier */
 
-#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32, the list steps, mvn_vnet_byword_step_states_f32, mvn_vnet_byword_step_max_symbols) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
+#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32, the list steps, mvn_vnet_byword_step_states_f32, mvn_vnet_byword_step_max_symbols, mvn_vnet_byword_step_states_list_f32, mvn_vnet_byword_step_list_max_symbols) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
 
 /* ABI version of the loaded library (== MVN_ABI_VERSION). */
 int mvn_version(void);
@@ -512,6 +512,40 @@ int mvn_va_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx,
                                 float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                 int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
                                 int64_t delta_ld, int32_t *choice, mvn_stream_t stream);
+
+/*
+ * mvn_vnet_byword_step_list_f32 for the ViterbiNet detector at S = 4, 8, 32, 64 or 128 states (S = 16 forwards to it, with its codes):
+ * same arguments, same outputs, one launch, a workgroup per word with the word's own weights.  The definition is the one above with
+ * 16 replaced by S, all in fp32 with every operation rounded on its own, cost[t][s] = -logit[t][s] of mvn_vnet_logits_f32:
+ *   alpha_0 = 0, alpha_{t+1}[s] = min(alpha_t[2s % S] + cost[t][2s % S], alpha_t[(2s+1) % S] + cost[t][(2s+1) % S])
+ *   dec     = what mvn_vnet_byword_step_states_path_f32 returns, bit for bit (torch.min's survivor, torch.argmin of the final metric)
+ *   beta_T = 0, beta_t[p] = cost[t][p] + min(beta_{t+1}[p >> 1], beta_{t+1}[(p >> 1) | S / 2])
+ *   delta_t = min_{s odd}(alpha_t[s] + beta_t[s]) - min_{s even}(alpha_t[s] + beta_t[s])
+ *   rho, the ranking by (rho, j), U, candidates 0 .. C(list_bytes, nsym), erasure filling and choice: as above
+ *   M(c) = sum_t cost[t][state_t(c)], ascending t, state_t = calculate_states with memory length log2 S; the labels likewise.
+ * (On chip the kernel keeps alpha_t[s] for s < S / 2 only -- states s and s + S / 2 share their predecessors -- and forms delta from
+ * alpha_t[s] + min(beta_t[s], beta_t[s + S / 2]): rounded addition is monotone, so this is the value above bit for bit on finite
+ * costs.)
+ * Logits, the alpha half-image and the survivors stay in LDS, 4 S + 2 S + 4 bytes per symbol (8 above 32 states), and bound the
+ * word: T <= mvn_vnet_byword_step_list_max_symbols(S) = min(512, what a CU's 160 KB hold next to the static part, in whole bytes)
+ * -- 512 at 4, 8, 16 and 32 states, 352 at 64, 160 at 128; 0 for a state count the step does not serve.
+ * The check, in the order of the steps above: S not in {4, 8, 16, 32, 64, 128} -> MVN_E_STATES; R < 0, T not a multiple of 8,
+ * T / 8 <= nsym, nsym outside 1 .. 8, T > mvn_vnet_byword_step_list_max_symbols(S), list_bytes outside nsym .. T / 8,
+ * C(list_bytes, nsym) > 63 or delta_ld < T -> MVN_E_DIMS; a leading dimension too small -> MVN_E_DIMS; R = 0 -> MVN_OK; a required
+ * pointer NULL -> MVN_E_NULL (tx may be NULL on a data step when nerr, label_word and labels are NULL).
+ * A pilot step is mvn_vnet_byword_step_states_f32's pilot step, after the list's own limits were checked (delta and choice are not
+ * written).  mvn_vnet_byword_step_list_f32 itself keeps answering MVN_E_STATES for S != 16.
+ * Non-finite costs: dec keeps the path step's rules; the launch stays memory-safe and deterministic, every rank, position, state
+ * and candidate index stays in range; delta and choice are unspecified.
+ * (Added without a bump of MVN_ABI_VERSION, like the other steps.)
+ */
+int32_t mvn_vnet_byword_step_list_max_symbols(int32_t S);
+int mvn_vnet_byword_step_states_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                         const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                         float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                         float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                         int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                         int64_t delta_ld, int32_t *choice, mvn_stream_t stream);
 
 /* The MVN_* environment switches (A/B variants of the kernels) are read once per process; a caller that
  * changes them afterwards (the test-suite does) calls this to have them read again. */

@@ -72,6 +72,8 @@ SIGNATURES = {
     "mvn_vnet_byword_step_path_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_va_byword_step_path_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_vnet_byword_step_list_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
+    "mvn_vnet_byword_step_list_max_symbols": (_i32, [_i32]),
+    "mvn_vnet_byword_step_states_list_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
     "mvn_va_byword_step_list_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
     "mvn_reload_switches": (None, []),
     "mvn_isi_awgn_transmit": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, ctypes.c_double, _vp, _i64, _i64,
@@ -175,15 +177,26 @@ def step_max_symbols(n_states: int) -> int:
     return int(load().mvn_vnet_byword_step_max_symbols(n_states))
 
 
+def list_max_symbols(n_states: int) -> int:
+    """The longest word the ViterbiNet list step serves at n_states (mvn_vnet_byword_step_list_max_symbols; 512 at 16 states, 0: not
+    served)."""
+    return int(load().mvn_vnet_byword_step_list_max_symbols(n_states))
+
+
 class BywordStep:
     """One of the by-word block steps of include/mvn.h, mvn_{kind}_byword_step[_path|_list]_f32 (kind 'vnet' / 'va', decision
     'running' / 'path' / 'list'), for words of T symbols with nsym parity bytes (list: list_bytes least reliable bytes): the symbol
     and the constant part of its argument list are resolved here, once, outside a caller's block loop.
     n_states other than 16: mvn_vnet_byword_step_states_f32, the ViterbiNet running step, and with states_path=True (what
-    harness._block_step and trials._cohort_steps pass) mvn_vnet_byword_step_states_path_f32 for decision 'path'; ValueError else."""
-    def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None, n_states: int = 16, states_path: bool = False):
+    harness._block_step and trials._cohort_steps pass) mvn_vnet_byword_step_states_path_f32 for decision 'path'; with
+    states_list=True (what they pass as well) mvn_vnet_byword_step_states_list_f32 for kind 'vnet', decision 'list' at the state
+    counts of STEP_STATES; ValueError else."""
+    def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None, n_states: int = 16, states_path: bool = False,
+                 states_list: bool = False):
         self.name = "mvn_%s_byword_step%s_f32" % (kind, {"running": "", "path": "_path", "list": "_list"}[decision])
-        if n_states != 16:
+        if states_list and kind == "vnet" and decision == "list" and n_states in STEP_STATES:
+            self.name = "mvn_vnet_byword_step_states_list_f32"
+        elif n_states != 16:
             if kind != "vnet" or decision not in (("running", "path") if states_path else ("running",)):
                 raise ValueError(f"the block step at {n_states} states is the ViterbiNet running step (kind='vnet', decision='running'; "
                                  f"states_path=True: decision='path' as well), not kind={kind!r}, decision={decision!r}")

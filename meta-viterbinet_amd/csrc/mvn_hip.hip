@@ -18,6 +18,7 @@
 //   va16_quad.inc, va_inplace.inc          fused classical Viterbi (16 states; any S >= 4)
 //   rs_codec.inc                           Reed-Solomon encode/decode
 //   byword_step.inc, byword_step_states.inc  one block step of the by-word evaluation in one launch (16 states; 4 ... 128 states)
+//   byword_list_states.inc                 that step with the list decode at 4 ... 128 states
 //   online_train.inc, maml_train.inc       one-launch online training and MAML meta-learning steps
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -471,6 +472,7 @@ int ensure_dynamic_lds(const void *fn, size_t bytes);  // raises a kernel's dyna
 #include "rs_codec.inc"
 #include "byword_step.inc"
 #include "byword_step_states.inc"
+#include "byword_list_states.inc"
 #include "online_train.inc"
 #include "maml_train.inc"
 #include "train_groups.inc"
@@ -1252,16 +1254,31 @@ int states_step_max_symbols(int32_t S) {
     }
 }
 
+// the longest word mvn_vnet_byword_step_states_list_f32 serves at S states (0: a state count it does not serve; 16 states: the step it
+// forwards to)
+int states_list_step_max_symbols(int32_t S) {
+    switch (S) {
+        case 4: return states_list_max_symbols<4>();
+        case 8: return states_list_max_symbols<8>();
+        case 16: return kListMaxT;
+        case 32: return states_list_max_symbols<32>();
+        case 64: return states_list_max_symbols<64>();
+        case 128: return states_list_max_symbols<128>();
+        default: return 0;
+    }
+}
+
 // The checks of a step, in the order the codes are documented in: the state count; the shapes; the list's limits; every leading
 // dimension; the rows of priors (VA); nothing to do (R = 0: MVN_OK before any pointer is looked at); the pointers.  A pilot detects
 // nothing, so a pilot of any decision is the running step and is checked as one: it needs tx and neither rx nor the priors (the
 // ViterbiNet weights are required all the same); only a list data step can do without tx, as long as nothing is compared with it.
 // Leaves the list's number of candidates in c.list.ncand.  any_states: the ViterbiNet running and path steps of
-// byword_step_states.inc, whose state counts and longest word are states_step_max_symbols'.
+// byword_step_states.inc, whose state counts and longest word are states_step_max_symbols', and the list step of
+// byword_list_states.inc, whose longest word is states_list_step_max_symbols' (a pilot's too: the list's limits come first).
 int step_check(StepCall &c, StepDecision decision, StepDetector detector, bool any_states = false) {
     const StepOut &o = c.out;
     const int T = c.T, nsym = c.nsym;
-    const int max_T = any_states ? states_step_max_symbols(c.S) : kCoopMaxT;
+    const int max_T = !any_states ? kCoopMaxT : decision == kStepList ? states_list_step_max_symbols(c.S) : states_step_max_symbols(c.S);
     if (any_states ? max_T == 0 : c.S != 16) return MVN_E_STATES;  // (the six steps of byword_step.inc exist for the 16-state detectors)
     if (c.R < 0 || T < 8 || (T & 7) || T > max_T || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
     if (decision == kStepList) {
@@ -1333,10 +1350,17 @@ int step_run(StepCall c, StepDecision decision, StepDetector detector) {
                        std::tuple_cat(head, list));
 }
 
-// mvn_vnet_byword_step_states_f32 / mvn_vnet_byword_step_states_path_f32 at S != 16: one launch of byword_step_states_kernel<S, NS> or
-// byword_path_step_states_kernel<S, NS>, R workgroups of kStatesWaves waves, the logit image (a data step's) as dynamic LDS
+// mvn_vnet_byword_step_states_f32 / mvn_vnet_byword_step_states_path_f32 / mvn_vnet_byword_step_states_list_f32 at S != 16: one launch
+// of byword_step_states_kernel<S, NS>, byword_path_step_states_kernel<S, NS> or byword_list_step_states_kernel<S, NS>, R workgroups of
+// kStatesWaves waves, the logit image (a data step's; the list's with its alpha half-image and survivors) as dynamic LDS
 template <int S, class Head>
 int states_step_launch(const StepCall &c, StepDecision decision, const Head &head) {
+    if (decision == kStepList) {
+        const ListOut &l = c.list;
+        return step_launch(byword_list_step_states_kernel<S, 2>, byword_list_step_states_kernel<S, 8>, c, 64 * kStatesWaves,
+                           (size_t)c.T * states_list_symbol_bytes<S>(), (size_t)states_list_max_symbols<S>() * states_list_symbol_bytes<S>(),
+                           std::tuple_cat(head, std::make_tuple(l.delta, l.delta_ld, l.choice, c.T, c.nsym, l.m, l.ncand)));
+    }
     const size_t dyn = c.pilot ? 0 : (size_t)c.T * S * sizeof(float), dyn_max = (size_t)states_max_symbols<S>() * S * sizeof(float);
     if (decision == kStepPath)
         return step_launch(byword_path_step_states_kernel<S, 2>, byword_path_step_states_kernel<S, 8>, c, 64 * kStatesWaves, dyn, dyn_max,
@@ -1348,7 +1372,7 @@ int states_step_launch(const StepCall &c, StepDecision decision, const Head &hea
 int states_step_run(StepCall c, StepDecision decision) {
     const int e = step_check(c, decision, kStepVnet, true);
     if (e != MVN_OK || c.R == 0) return e;
-    if (c.pilot) decision = kStepRunning;  // (the path kernel is a data step)
+    if (c.pilot) decision = kStepRunning;  // (the path and list kernels are data steps)
     const StepOut &o = c.out;
     WeightStrides ws;
     for (int a = 0; a < 6; ++a) ws.s[a] = c.w_stride ? (long long)c.w_stride[a] : 0;
@@ -1837,6 +1861,24 @@ int mvn_vnet_byword_step_states_path_f32(const float *rx, int64_t rx_ld, const f
     return states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
                             {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
                            kStepPath);
+}
+
+int32_t mvn_vnet_byword_step_list_max_symbols(int32_t S) { return states_list_step_max_symbols(S); }
+
+int mvn_vnet_byword_step_states_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                         const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                         float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                         float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                         int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                         int64_t delta_ld, int32_t *choice, mvn_stream_t stream) {
+    if (S == 16)
+        return mvn_vnet_byword_step_list_f32(rx, rx_ld, tx, tx_ld, W1, b1, W2, b2, W3, b3, w_stride, dec, dec_ld, msg, msg_ld, enc, enc_ld,
+                                             label_word, lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, list_bytes, delta, delta_ld,
+                                             choice, stream);
+    return states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr},
+                            {delta, delta_ld, choice, list_bytes, 0}, {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S,
+                            (hipStream_t)stream},
+                           kStepList);
 }
 
 int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,

@@ -343,7 +343,9 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     (mvn_vnet_byword_step_list_f32 / mvn_va_byword_step_list_f32; list_bytes = how many least reliable bytes the erasure patterns
     are drawn from, default n_symbols + 2): the message is the candidate the trellis likes best, and the error count, the re-encoded
     word and the buffered label word follow from it.  It exists in the one-launch step only: ValueError when the step's conditions
-    (_fused_step_applies, fused_step=True) or T <= 512 do not hold."""
+    (_fused_step_applies, fused_step=True) or T <= 512 do not hold.  A ViterbiNet detector at 4, 8, 32, 64 or 128 states takes
+    mvn_vnet_byword_step_states_list_f32 (_states_list_step_applies: the path step's conditions and words up to
+    _lib.list_max_symbols(n_states) symbols); 2 and 256 states and a VADetector off 16 states have no list step."""
     import copy
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
@@ -369,7 +371,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     N = tx.shape[0]
     ser_by_word = np.zeros(N)
     K = tx.shape[1]
-    fused = fused_step and _fused_step_applies(detector, rx, n_symbols, pass_count, decision)
+    fused = fused_step and (_fused_step_applies(detector, rx, n_symbols, pass_count, decision)
+                            or (decision == "list" and _states_list_step_applies(detector, rx, n_symbols, pass_count)))
     if decision == "list":
         list_bytes = _list_step_bytes(detector, rx, n_symbols, pass_count, fused_step, list_bytes)
     elif list_bytes is not None:
@@ -594,9 +597,20 @@ def _fused_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: 
     return isinstance(detector, VADetector) and detector.transmission_length == T and (pass_count or detector.val_words == 1)
 
 
+def _states_list_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool) -> bool:
+    """decision='list' off 16 states: a VNETDetector at 4, 8, 32, 64 or 128 states under the path step's conditions
+    (_fused_step_applies) takes mvn_vnet_byword_step_states_list_f32 for words up to _lib.list_max_symbols(n_states) symbols."""
+    from . import _lib
+
+    S = getattr(detector, "n_states", None)
+    return (S in _lib.STEP_STATES and _fused_step_applies(detector, rx, n_symbols, pass_count, "path")
+            and rx.shape[1] <= _lib.list_max_symbols(S))
+
+
 def _list_step_bytes(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, fused_step: bool, list_bytes) -> int:
     """decision='list' exists in the one-launch block step only: the validated list_bytes, or a ValueError that names the
     condition that does not hold (there is no other route to fall back to)."""
+    from . import _lib
     from .detectors import VADetector, VNETDetector
 
     T = rx.shape[1]
@@ -605,8 +619,13 @@ def _list_step_bytes(detector, rx: torch.Tensor, n_symbols: int, pass_count: boo
         raise ValueError("decision='list' runs in the one-launch block step: fused_step=False has no list decoder")
     if not rx.is_cuda:
         raise ValueError("decision='list' needs the received words on an MI355X (ROCm) device")
-    if getattr(detector, "n_states", None) != 16:
-        raise ValueError("decision='list' needs a 16-state detector")
+    S = getattr(detector, "n_states", None)
+    if S in _lib.STEP_STATES and isinstance(detector, VNETDetector):
+        if T > _lib.list_max_symbols(S):
+            raise ValueError(f"decision='list' serves words of up to {_lib.list_max_symbols(S)} symbols at {S} states (logits, forward "
+                             f"metrics and survivors stay in LDS), got T = {T}")
+    elif S != 16:
+        raise ValueError("decision='list' needs a 16-state detector, or a ViterbiNet detector at 4, 8, 32, 64 or 128 states")
     if isinstance(detector, VNETDetector):
         if pass_count:
             raise ValueError("decision='list': a ViterbiNet detector takes no block number (pass_count=False)")
@@ -619,7 +638,7 @@ def _list_step_bytes(detector, rx: torch.Tensor, n_symbols: int, pass_count: boo
             raise ValueError("decision='list': a VADetector with several rows of state priors needs pass_count=True")
     else:
         raise ValueError(f"decision='list' needs a VNETDetector or a VADetector, not {type(detector).__name__}")
-    assert _fused_step_applies(detector, rx, n_symbols, pass_count)
+    assert _fused_step_applies(detector, rx, n_symbols, pass_count) if S == 16 else _states_list_step_applies(detector, rx, n_symbols, pass_count)
     return m
 
 
@@ -629,7 +648,7 @@ def _block_step(detector, T: int, n_symbols: int, decision: str, list_bytes):
     from .detectors import VADetector
 
     return _lib.BywordStep("va" if isinstance(detector, VADetector) else "vnet", decision, T, n_symbols, list_bytes,
-                           n_states=detector.n_states, states_path=True)
+                           n_states=detector.n_states, states_path=True, states_list=True)
 
 
 def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, pilot: bool, nerr: torch.Tensor,

@@ -223,7 +223,7 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     bank and R >= META_TRIAL_AXIS_MIN_R = 2 -- one trial has nothing to batch and goes through harness.eval_by_word, whose updates
     run on the one-trial kernel maml_train_kernel<64 | 128, false>; True takes it whenever it serves the bank, R = 1 included;
     False never takes it (every trial through harness.eval_by_word, one after the other).  Same rows either way.  The keyword
-    changes nothing where the route does not apply: up to 32 states, 256 states, RMSprop / SGD with online_meta, decision='list',
+    changes nothing where the route does not apply: up to 32 states, 256 states, RMSprop / SGD with online_meta,
     longer words, no online_meta; an LSTM bank accepts and ignores it.
     cohorts > 1: the trials are split into that many groups that step ALTERNATELY on the same stream: while the GPU works
     through one group's training launches the host takes the decisions and fills the descriptors of the next (the host
@@ -242,7 +242,9 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
     (harness.eval_by_word(decision='path')): the lock-step block step is mvn_vnet_byword_step_path_f32 for all R trials
     (mvn_vnet_byword_step_states_path_f32 at 4, 8, 32, 64 and 128 states), the trial-after-trial route passes the keyword on; an LSTM bank raises ValueError.
     decision='list': the path's word, list-decoded in the same launch (mvn_vnet_byword_step_list_f32 for all R trials; list_bytes
-    as in harness.eval_by_word, default n_symbols + 2).  It needs the 16-state step and words of at most 512 symbols: ValueError
+    as in harness.eval_by_word, default n_symbols + 2; at 4, 8, 32, 64 and 128 states mvn_vnet_byword_step_states_list_f32, lock
+    step wherever decision='path' would go lock step for the same bank, trial after trial through harness.eval_by_word otherwise).
+    It needs one of these state counts and words of at most _lib.list_max_symbols(n_states) symbols (512 at 16 states): ValueError
     otherwise, there is no other route."""
     from .lstm_trials import LSTMTrialBank
 
@@ -257,8 +259,11 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
         from .ecc import list_step_bytes
 
         list_bytes = list_step_bytes(rx.shape[2], n_symbols, list_bytes)
-        if bank.n_states != 16:
-            raise ValueError("decision='list' needs a 16-state detector")
+        if bank.n_states != 16 and bank.n_states not in _lib.STEP_STATES:
+            raise ValueError("decision='list' needs a ViterbiNet bank at 4, 8, 16, 32, 64 or 128 states")
+        if bank.n_states != 16 and rx.shape[2] > _lib.list_max_symbols(bank.n_states):
+            raise ValueError(f"decision='list' serves words of up to {_lib.list_max_symbols(bank.n_states)} symbols at {bank.n_states} "
+                             f"states, got T = {rx.shape[2]}")
         if not rx.is_cuda:
             raise ValueError("decision='list' needs the received words on an MI355X (ROCm) device")
     elif list_bytes is not None:
@@ -285,10 +290,12 @@ def eval_by_word_batched(bank: TrialBank, tx: torch.Tensor, rx: torch.Tensor, n_
                                         ser_thresh, online_meta, meta_lr, MAML, window_size, meta_train_iterations, meta_j_num,
                                         meta_subframes, meta_style_online_training, weights_init, meta_training_weights, record,
                                         initial_buffer)
+    # the list step off 16 states goes lock step wherever the path step would (the word fits it: checked above)
+    served_as = "path" if decision == "list" and bank.n_states != 16 else decision
     meta_states = (meta_trial_axis is not False and (meta_trial_axis or R >= META_TRIAL_AXIS_MIN_R)
-                   and _meta_states_serves(bank.n_states, rx, n_symbols, decision, online_meta, bank.optimizer_type))
+                   and _meta_states_serves(bank.n_states, rx, n_symbols, served_as, online_meta, bank.optimizer_type))
     if (bank.optimizer_type != "Adam" and online_meta) or not (
-            meta_states or _lock_step_serves(bank.n_states, rx, n_symbols, decision, online_meta)):
+            meta_states or _lock_step_serves(bank.n_states, rx, n_symbols, served_as, online_meta)):
         return _one_trial_at_a_time(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_word, record, initial_buffer,
                                     dict(self_supervised=self_supervised, self_supervised_iterations=self_supervised_iterations,
                                          ser_thresh=ser_thresh, online_meta=online_meta, meta_lr=meta_lr, MAML=MAML, window_size=window_size,
@@ -399,7 +406,8 @@ def _cohort_steps(bank, tx, rx, n_symbols, subframes_in_frame, draws, ser_by_wor
     host has to wait for before it can decide what the trials do next (eval_by_word_batched drives one or more of these)."""
     _lib.require_gpu_tensor(rx, "rx")
     lib = _lib.load()
-    step = _lib.BywordStep("vnet", decision, rx.shape[2], n_symbols, list_bytes, n_states=bank.n_states, states_path=True)
+    step = _lib.BywordStep("vnet", decision, rx.shape[2], n_symbols, list_bytes, n_states=bank.n_states, states_path=True,
+                           states_list=True)
     dev = rx.device
     R, N, T = rx.shape
     K = tx.shape[2]
