@@ -19,12 +19,18 @@
 // gridDim.x = R words, each with ITS OWN weights (word r uses W + r * stride): R independent trials of the evaluation
 // advance one block per launch (harness.eval_by_word_batched); R = 1 is the reference's sequential call pattern.
 //
-// The family is two detectors times three decision rules (StepDecision): six kernels.  They share the codec, byword_list_tail, the
-// detectors and path16_walk as code, and StepOut / ListOut as types: a kernel packs its output parameters where it calls the codec or
-// the list tail.  The structs travel BY VALUE and each kernel keeps its own staging, detection and finish lines and its LDS in the
-// __global__ function: a const reference to the structs, a reference to the LDS object in a shared staging or finish function, or
-// one more forceinline layer around a kernel's lines each change what the compiler emits for it (the traced-back kernels then measure
-// 1-2 % slower).  Share more here only with an unchanged disassembly of all twelve kernels.
+// The family is two detectors times three decision rules (StepDecision): six kernels here, twelve with NS = 2 and 8, and the three
+// of byword_step_states.inc / byword_list_states.inc at five more state counts.  They share the codec, byword_list_tail (ONE copy for
+// every state count: what differs off 16 states is chosen by if constexpr inside it), ListFields, the detectors and path16_walk as code,
+// and StepOut / ListOut as types: a kernel packs its output parameters where it calls the codec or the list tail.  The structs travel
+// BY VALUE and each kernel keeps its own staging, detection and finish lines and its LDS in the __global__ function: a const reference
+// to the structs, a reference to the LDS object in a shared staging or finish function, or one more forceinline layer around a
+// kernel's lines each change what the compiler emits for it (the traced-back kernels then measure 1-2 % slower).  Share more here only
+// with an unchanged disassembly of every by-word kernel, at every instantiation.  To check it, build the device assembly of the parent
+// commit and of the tree with the library's flags (__graft_entry__.py: HIPCC_FLAGS without -shared -fPIC) and compare them:
+//     hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 --cuda-device-only -S mvn_hip.hip -o tree.s     (parent.s alike)
+//     python tools/kernel_isa_diff.py parent.s tree.s        ("same N diff 0"; once more with -DMVN_TEST_HOOKS)
+// profiles/byword_isa_identity.txt holds that output for the change that made the list tail and the sweep-and-walk one copy each.
 struct WeightStrides {
     long long s[6];  // elements between consecutive words' W1, b1, W2, b2, W3, b3 (0: all words share one set)
 };
@@ -367,14 +373,18 @@ constexpr int kListMaxT = 512;
 constexpr int kListMaxCand = 63;    // candidates 1 .. 63 next to the hard decoder's: one wave
 constexpr int kCandStride = 68;     // bytes between the candidates' codewords: 17 dwords, the lanes' byte reads spread over the banks
 
-template <int NS>
-struct ListStepShared : PathStepShared<NS> {
+// The list's own LDS, ONCE, on top of the step it extends: ListStepShared<NS> at 16 states, StatesListShared<S, NS>
+// (byword_list_states.inc) at the other state counts.
+template <class Base>
+struct ListFields : Base {
     float delta[kListMaxT];
     float rho[64];
     __attribute__((aligned(4))) unsigned char raw[kRsRow];  // dec as bytes
     unsigned char order[64];                                // byte positions by rank
     __attribute__((aligned(4))) unsigned char cand[64 * kCandStride];
 };
+template <int NS>
+using ListStepShared = ListFields<PathStepShared<NS>>;
 
 __device__ __forceinline__ int list_binom(int a, int b) {  // C(a, b), every partial product a binomial itself
     if (b < 0 || b > a) return 0;
@@ -383,15 +393,18 @@ __device__ __forceinline__ int list_binom(int a, int b) {  // C(a, b), every par
     return c;
 }
 
-// Everything of a list step after the walk, by ONE wave: sh.dbits = dec, cost / alpha = the [t][16] images, sh.gf / sh.gen / sh.txrow
-// as for byword_codec.  lo.ncand = C(lo.m, nsym).
-template <int NS>
-__device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const float *cost, float *alpha, int64_t r, int lane,
-                                                 StepOut out, ListOut lo, int T, int nsym) {
+// Everything of a list step after the walk, by ONE wave, at every state count: sh.dbits = dec, sh.gf / sh.gen / sh.txrow as for
+// byword_codec.  lo.ncand = C(lo.m, nsym).  S = 16: cost / alpha = the [t][16] images.  Any other S (byword_list_states.inc, which
+// states the forms): cost = the LOGIT image [t][S] (cost = -logit), alpha = the half-image [t][S / 2].  Three pieces differ with S, each
+// as its family had it: the beta recursion, the delta loop, the candidate's state and cost look-up; everything else is one copy.
+template <int NS, int S = 16, class Shared>
+__device__ __forceinline__ void byword_list_tail(Shared &sh, const float *cost, float *alpha, int64_t r, int lane, StepOut out,
+                                                 ListOut lo, int T, int nsym) {
+    constexpr int H = S / 2, MEM = __builtin_ctz(S);
     const int n = T >> 3, m = lo.m, ncand = lo.ncand;
-    // ---- beta, and alpha + beta in place: lanes 0..15, one per state (the other lanes take part in the cross-lane reads only; what
-    // they hold is never read)
-    {
+    if constexpr (S == 16) {
+        // ---- beta, and alpha + beta in place: lanes 0..15, one per state (the other lanes take part in the cross-lane reads only;
+        // what they hold is never read)
         const int s = lane & 15, src0 = s >> 1, src1 = src0 | 8;
         const bool mine = lane < 16;
         float beta = 0.0f;
@@ -409,17 +422,43 @@ __device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const f
             c = cn;
             a = an;
         }
+    } else {
+        // ---- beta, and alpha + gamma in place: lane h (and every lane that repeats it) holds states h and h + S / 2
+        const int h = lane % H, src0 = h >> 1, src1 = src0 + H / 2;  // the lanes that hold gamma[p >> 1] of p = h and of p = h + S / 2
+        float g = 0.0f;                                              // gamma_{t+1}; beta_T = 0
+        float c0 = -cost[(T - 1) * S + h], c1 = -cost[(T - 1) * S + h + H], a = alpha[(T - 1) * H + h];
+        for (int t = T - 1; t >= 0; --t) {
+            const int tn = t > 0 ? t - 1 : 0;
+            const float n0 = -cost[tn * S + h], n1 = -cost[tn * S + h + H], an = alpha[tn * H + h];  // the next step's operands, off the chain
+            const float g0 = __shfl(g, src0), g1 = __shfl(g, src1);
+            const float b0 = c0 + g0, b1 = c1 + g1;
+            g = fminf(b0, b1);
+            if (lane < H) alpha[t * H + h] = a + g;
+            c0 = n0;
+            c1 = n1;
+            a = an;
+        }
     }
     wave_lds_fence();
-    // ---- delta, one lane per symbol; the lane's 16 reads start at its own state so that the rows of a wave spread over the banks
+    // ---- delta, one lane per symbol; the lane's reads start at its own state so that the rows of a wave spread over the banks
     for (int t = lane; t < T; t += 64) {
         float mo = __builtin_inff(), me = __builtin_inff();
+        if constexpr (S == 16) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int s = (i + lane) & 15;
-            const float v = alpha[t * 16 + s];
-            if (s & 1) mo = fminf(mo, v);
-            else me = fminf(me, v);
+            for (int i = 0; i < 16; ++i) {
+                const int s = (i + lane) & 15;
+                const float v = alpha[t * 16 + s];
+                if (s & 1) mo = fminf(mo, v);
+                else me = fminf(me, v);
+            }
+        } else {
+#pragma unroll 8
+            for (int i = 0; i < H; ++i) {
+                const int s = (i + lane) & (H - 1);
+                const float v = alpha[t * H + s];
+                if (s & 1) mo = fminf(mo, v);
+                else me = fminf(me, v);
+            }
         }
         const float d = mo - me;
         sh.delta[t] = d;
@@ -485,12 +524,22 @@ __device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const f
         for (int jb = 0; jb < n; ++jb) {
             const int cur = nxt;
             nxt = jb + 1 < n ? mine[jb + 1] : 0;
-            const int w = (cur << 8) | nxt;
+            if constexpr (S == 16) {
+                const int w = (cur << 8) | nxt;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int nib = (w >> (12 - i)) & 15;                                   // b[t] b[t+1] b[t+2] b[t+3], b[t] highest
-                const int st = (int)((0xF7B3D591E6A2C480ull >> (4 * nib)) & 15);       // its bits reversed: sum_i 2^i b[t + i]
-                M = M + cost[(8 * jb + i) * 16 + st];
+                for (int i = 0; i < 8; ++i) {
+                    const int nib = (w >> (12 - i)) & 15;                              // b[t] b[t+1] b[t+2] b[t+3], b[t] highest
+                    const int st = (int)((0xF7B3D591E6A2C480ull >> (4 * nib)) & 15);  // its bits reversed: sum_i 2^i b[t + i]
+                    M = M + cost[(8 * jb + i) * 16 + st];
+                }
+            } else {
+                const unsigned w = (unsigned)((cur << 8) | nxt);  // b[8 jb] is bit 15
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const unsigned f = (w >> (16 - MEM - i)) & (unsigned)(S - 1);  // b[t] ... b[t + MEM - 1], b[t] highest
+                    const int st = (int)(__brev(f) >> (32 - MEM));                // its bits reversed: sum_i 2^i b[t + i]
+                    M = M + -cost[(8 * jb + i) * S + st];
+                }
             }
         }
     }
@@ -511,7 +560,7 @@ __device__ __forceinline__ void byword_list_tail(ListStepShared<NS> &sh, const f
     if (best != 0)
         for (int p = lane; p < n; p += 64) sh.row[p] = sh.cand[best * kCandStride + p];
     wave_lds_fence();
-    byword_codec<NS, true>(sh, r, lane, out, T, nsym, 0);
+    byword_codec<NS, true, MEM>(sh, r, lane, out, T, nsym, 0);
 }
 
 template <int NS>

@@ -35,6 +35,39 @@ struct StatesStepShared : StepShared<NS> {
     float b3[StatesCfg<S>::NT3 * 16];
 };
 
+// Phase 1 of the three kernels of this family (the running and the path step below, the list step of byword_list_states.inc): the
+// word's tiles, round-robin over the waves, into states_logit[t][S].  ONE copy as TEXT, and only as text: it expands in the kernel's
+// own body and reads the kernel's parameters rx, rx_ld, W1 .. b3, ws, T and its locals C, sh, states_logit, r, lane, wave by name, so
+// the compiler sees the lines where they always stood.  A __forceinline__ function around them changes the emitted code of all thirty
+// kernels (tools/kernel_isa_diff.py: scalar address arithmetic and the schedule of the tile phase, in the first ~1 800 lines of
+// each) -- with the pointers offset at the call; with raw pointers, WeightStrides by value and r, offset inside in the original order;
+// and the same with __restrict__ parameters.  byword_step.inc's rule is unchanged code, so none of them was taken.
+#define MVN_STATES_PHASE1()                                                                                                      \
+    {                                                                                                                            \
+        const int j = lane & 15, q = lane >> 4;                                                                                  \
+        const float *rxb = rx + r * rx_ld;                                                                                       \
+        mlp_stage_w3<C::NT3>(sh.a3, sh.b3, W3 + r * ws.s[4], b3 + r * ws.s[5], S);                                               \
+        float nw1[kK2Steps], nb1[kK2Steps], a2[4][kK2Steps], b2v[4][4];                                                          \
+        mlp_load_weights(W1 + r * ws.s[0], b1 + r * ws.s[1], W2 + r * ws.s[2], b2 + r * ws.s[3], j, q, nw1, nb1, a2, b2v);       \
+        __syncthreads();                                                                                                         \
+        const int ntiles = (T + 15) >> 4;                                                                                        \
+        for (int tile = wave; tile < ntiles; tile += kStatesWaves) {                                                             \
+            const int t = 16 * tile + j;                                                                                         \
+            const float yj = rxb[t < T ? t : T - 1];                                                                             \
+            mlp_tile<C::NT3>(yj, nw1, nb1, a2, b2v, sh.a3, lane, [&](int j3, f32x4 acc3) {                                       \
+                const int st0 = 16 * j3 + 4 * q;                                                                                 \
+                if (st0 < S && t < T) { /* (S is a multiple of 4: the lane's four states are all the trellis's or none) */       \
+                    float4 v;                                                                                                    \
+                    v.x = acc3[0] + sh.b3[st0 + 0];                                                                              \
+                    v.y = acc3[1] + sh.b3[st0 + 1];                                                                              \
+                    v.z = acc3[2] + sh.b3[st0 + 2];                                                                              \
+                    v.w = acc3[3] + sh.b3[st0 + 3];                                                                              \
+                    *reinterpret_cast<float4 *>(&states_logit[t * S + st0]) = v;                                                 \
+                }                                                                                                                \
+            });                                                                                                                  \
+        }                                                                                                                        \
+    }
+
 // the longest word the step serves at S states: what the LDS holds next to the larger (NS = 8) static part, in whole bytes of
 // eight symbols, and no more than the step's own limit (StepShared's images)
 template <int S>
@@ -134,31 +167,7 @@ __global__ __launch_bounds__(64 * kStatesWaves) void byword_step_states_kernel(
         const float *txb = tx + r * tx_ld;
         for (int p = blockDim.x - 1 - threadIdx.x; p < k; p += blockDim.x) sh.txrow[p] = (unsigned char)pack_byte(txb + 8 * p);
     }
-    if (!pilot) {
-        // ---- phase 1: the word's tiles, round-robin over the waves
-        const int j = lane & 15, q = lane >> 4;
-        const float *rxb = rx + r * rx_ld;
-        mlp_stage_w3<C::NT3>(sh.a3, sh.b3, W3 + r * ws.s[4], b3 + r * ws.s[5], S);
-        float nw1[kK2Steps], nb1[kK2Steps], a2[4][kK2Steps], b2v[4][4];
-        mlp_load_weights(W1 + r * ws.s[0], b1 + r * ws.s[1], W2 + r * ws.s[2], b2 + r * ws.s[3], j, q, nw1, nb1, a2, b2v);
-        __syncthreads();
-        const int ntiles = (T + 15) >> 4;
-        for (int tile = wave; tile < ntiles; tile += kStatesWaves) {
-            const int t = 16 * tile + j;
-            const float yj = rxb[t < T ? t : T - 1];
-            mlp_tile<C::NT3>(yj, nw1, nb1, a2, b2v, sh.a3, lane, [&](int j3, f32x4 acc3) {
-                const int st0 = 16 * j3 + 4 * q;
-                if (st0 < S && t < T) {  // (S is a multiple of 4: the lane's four states are all the trellis's or none)
-                    float4 v;
-                    v.x = acc3[0] + sh.b3[st0 + 0];
-                    v.y = acc3[1] + sh.b3[st0 + 1];
-                    v.z = acc3[2] + sh.b3[st0 + 2];
-                    v.w = acc3[3] + sh.b3[st0 + 3];
-                    *reinterpret_cast<float4 *>(&states_logit[t * S + st0]) = v;
-                }
-            });
-        }
-    }
+    if (!pilot) MVN_STATES_PHASE1()  // ---- phase 1: the word's tiles, round-robin over the waves
     __syncthreads();
     if (wave != 0) return;
     if (!pilot) {
@@ -176,8 +185,8 @@ __global__ __launch_bounds__(64 * kStatesWaves) void byword_step_states_kernel(
 }
 
 // ---- The same step on the TRACED-BACK PATH (mvn_vnet_byword_step_states_path_f32): byword_path_step_kernel's counterpart at these
-// state counts.  A data step in the frame above, unchanged (the kernel keeps its own copy of the staging and tile lines, as the
-// kernels of byword_step.inc do); what differs is what the lone wave makes of the image.
+// state counts.  A data step in the frame above, unchanged (the kernel keeps its own staging lines, as the kernels of
+// byword_step.inc do, and expands MVN_STATES_PHASE1 in its own body); what differs is what the lone wave makes of the image.
 //   sweep   states_sweep_word's recurrence -- same candidates, same min2_torch_dev -- that also keeps torch.min's index as
 //           sweep_surv_kernel defines it: second = !(v1 >= v0) && v0 == v0, v0 the candidate of predecessor 2 s mod S (the first
 //           minimum, the first NaN).  States s and s + S / 2 have the same two predecessors, hence the same candidates and the same
@@ -192,11 +201,16 @@ __global__ __launch_bounds__(64 * kStatesWaves) void byword_step_states_kernel(
 //           load, a stage per lane, requested before the 32 stages above them are walked; the walk takes each word from its lane
 //           (readlane) and is scalar arithmetic, every lane alike.  Lane e of each 32 stages stores bit e to dbits and dec.
 // The survivor dwords travel through the float image as bit patterns (__uint_as_float: moves, no arithmetic touches them).
-template <int S>
-__device__ __forceinline__ void states_path_word(float *image, int T, int lane, unsigned char *dbits, float *__restrict__ dec) {
+// LIST (byword_list_states.inc): the image KEEPS its logits and is only read; a stage's ballot goes to `surv` (one dword per stage, two
+// when kWide), the walk fetches it from there, and the metric before stage t goes to the half-image alpha[t][S / 2].  The path form
+// takes neither (nullptr).
+template <int S, bool LIST = false>
+__device__ __forceinline__ void states_path_word(float *image, float *alpha, unsigned *surv, int T, int lane, unsigned char *dbits,
+                                                 float *__restrict__ dec) {
     using C = StatesCfg<S>;
-    constexpr int LPB = C::LPB, R = C::R, TC = 8, WK = 32;
+    constexpr int LPB = C::LPB, R = C::R, TC = 8, WK = 32, H = S / 2;
     constexpr bool kWide = S > 32;  // the survivors of a stage take two dwords
+    constexpr int SW = kWide ? 2 : 1;
     const int sl = lane % LPB;
     const int src0 = (2 * sl) % LPB, src1 = src0 + 1;
     float m = 0.0f;  // (128 states: a lane's two states end every stage with one value)
@@ -216,6 +230,8 @@ __device__ __forceinline__ void states_path_word(float *image, int T, int lane, 
         if (t0 + TC < T) load_chunk(t0 + TC, nxt);
 #pragma unroll
         for (int i = 0; i < TC; ++i) {
+            if constexpr (LIST)
+                if (lane < H) alpha[(t0 + i) * H + lane] = m;  // the metric before stage t0 + i of states lane and lane + S / 2
             float a[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) a[r] = m + -cur[i][r];
@@ -229,9 +245,14 @@ __device__ __forceinline__ void states_path_word(float *image, int T, int lane, 
             m = min2_torch_dev(v0, v1);
             const unsigned long long bal = __ballot(second);
             if (lane == 0) {
-                float *row = image + (t0 + i) * S;
-                row[0] = __uint_as_float((unsigned)bal);
-                if (kWide) row[1] = __uint_as_float((unsigned)(bal >> 32));
+                if constexpr (LIST) {
+                    surv[(t0 + i) * SW] = (unsigned)bal;
+                    if (kWide) surv[(t0 + i) * SW + SW - 1] = (unsigned)(bal >> 32);
+                } else {
+                    float *row = image + (t0 + i) * S;
+                    row[0] = __uint_as_float((unsigned)bal);
+                    if (kWide) row[1] = __uint_as_float((unsigned)(bal >> 32));
+                }
             }
         }
     }
@@ -256,8 +277,13 @@ __device__ __forceinline__ void states_path_word(float *image, int T, int lane, 
         const int t = base + (lane & (WK - 1));
         lo = hi = 0u;
         if (t >= 0) {
-            lo = __float_as_uint(image[t * S]);
-            if (kWide) hi = __float_as_uint(image[t * S + 1]);
+            if constexpr (LIST) {
+                lo = surv[t * SW];
+                if (kWide) hi = surv[t * SW + SW - 1];
+            } else {
+                lo = __float_as_uint(image[t * S]);
+                if (kWide) hi = __float_as_uint(image[t * S + 1]);
+            }
         }
     };
     unsigned clo, chi, nlo, nhi;
@@ -308,35 +334,11 @@ __global__ __launch_bounds__(64 * kStatesWaves) void byword_path_step_states_ker
         const float *txb = tx + r * tx_ld;
         for (int p = blockDim.x - 1 - threadIdx.x; p < k; p += blockDim.x) sh.txrow[p] = (unsigned char)pack_byte(txb + 8 * p);
     }
-    {
-        // ---- phase 1: the word's tiles, round-robin over the waves
-        const int j = lane & 15, q = lane >> 4;
-        const float *rxb = rx + r * rx_ld;
-        mlp_stage_w3<C::NT3>(sh.a3, sh.b3, W3 + r * ws.s[4], b3 + r * ws.s[5], S);
-        float nw1[kK2Steps], nb1[kK2Steps], a2[4][kK2Steps], b2v[4][4];
-        mlp_load_weights(W1 + r * ws.s[0], b1 + r * ws.s[1], W2 + r * ws.s[2], b2 + r * ws.s[3], j, q, nw1, nb1, a2, b2v);
-        __syncthreads();
-        const int ntiles = (T + 15) >> 4;
-        for (int tile = wave; tile < ntiles; tile += kStatesWaves) {
-            const int t = 16 * tile + j;
-            const float yj = rxb[t < T ? t : T - 1];
-            mlp_tile<C::NT3>(yj, nw1, nb1, a2, b2v, sh.a3, lane, [&](int j3, f32x4 acc3) {
-                const int st0 = 16 * j3 + 4 * q;
-                if (st0 < S && t < T) {
-                    float4 v;
-                    v.x = acc3[0] + sh.b3[st0 + 0];
-                    v.y = acc3[1] + sh.b3[st0 + 1];
-                    v.z = acc3[2] + sh.b3[st0 + 2];
-                    v.w = acc3[3] + sh.b3[st0 + 3];
-                    *reinterpret_cast<float4 *>(&states_logit[t * S + st0]) = v;
-                }
-            });
-        }
-    }
+    MVN_STATES_PHASE1()  // ---- phase 1: the word's tiles, round-robin over the waves
     __syncthreads();
     if (wave != 0) return;
     // ---- phase 2: wave 0 sweeps the word, walks its survivors back and carries on with the codec
-    states_path_word<S>(states_logit, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
+    states_path_word<S>(states_logit, nullptr, nullptr, T, lane, sh.dbits, dec ? dec + r * dec_ld : nullptr);
     if (!kClosedForm && lane == 0) rs_generator_poly<NS>(sh.gf, sh.gen, nsym);  // (after the workgroup barrier: tables complete)
     wave_lds_fence();
     byword_codec<NS, false, C::MEM>(sh, r, lane, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr_out}, T, nsym, 0);

@@ -1240,32 +1240,32 @@ int list_step_candidates(int32_t T, int32_t nsym, int32_t m) {
     return c <= kListMaxCand ? (int)c : 0;
 }
 
+// The state counts of byword_step_states.inc and byword_list_states.inc, in ONE place: fn(SC tag) picks the instantiation for S, as
+// dispatch_states does for the training kernels; `other` is the answer for every other count (16 states among them).
+template <class Fn>
+int dispatch_step_states(int S, int other, Fn fn) {
+    switch (S) {
+        case 4: return fn(std::integral_constant<int, 4>{});
+        case 8: return fn(std::integral_constant<int, 8>{});
+        case 32: return fn(std::integral_constant<int, 32>{});
+        case 64: return fn(std::integral_constant<int, 64>{});
+        case 128: return fn(std::integral_constant<int, 128>{});
+        default: return other;
+    }
+}
+
 // the longest word mvn_vnet_byword_step_states_f32 and mvn_vnet_byword_step_states_path_f32 serve at S states (0: a state count
 // they do not serve; 16 states: the steps they forward to)
 int states_step_max_symbols(int32_t S) {
-    switch (S) {
-        case 4: return states_max_symbols<4>();
-        case 8: return states_max_symbols<8>();
-        case 16: return kCoopMaxT;
-        case 32: return states_max_symbols<32>();
-        case 64: return states_max_symbols<64>();
-        case 128: return states_max_symbols<128>();
-        default: return 0;
-    }
+    if (S == 16) return kCoopMaxT;
+    return dispatch_step_states(S, 0, [](auto sc) { return states_max_symbols<decltype(sc)::value>(); });
 }
 
 // the longest word mvn_vnet_byword_step_states_list_f32 serves at S states (0: a state count it does not serve; 16 states: the step it
 // forwards to)
 int states_list_step_max_symbols(int32_t S) {
-    switch (S) {
-        case 4: return states_list_max_symbols<4>();
-        case 8: return states_list_max_symbols<8>();
-        case 16: return kListMaxT;
-        case 32: return states_list_max_symbols<32>();
-        case 64: return states_list_max_symbols<64>();
-        case 128: return states_list_max_symbols<128>();
-        default: return 0;
-    }
+    if (S == 16) return kListMaxT;
+    return dispatch_step_states(S, 0, [](auto sc) { return states_list_max_symbols<decltype(sc)::value>(); });
 }
 
 // The checks of a step, in the order the codes are documented in: the state count; the shapes; the list's limits; every leading
@@ -1378,14 +1378,7 @@ int states_step_run(StepCall c, StepDecision decision) {
     for (int a = 0; a < 6; ++a) ws.s[a] = c.w_stride ? (long long)c.w_stride[a] : 0;
     const auto head = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.W[0], c.W[1], c.W[2], c.W[3], c.W[4], c.W[5], ws, c.dec, c.dec_ld,
                                       o.msg, o.msg_ld, o.enc, o.enc_ld, o.label_word, o.lw_ld, o.labels, o.lab_ld, o.nerr);
-    switch (c.S) {
-        case 4: return states_step_launch<4>(c, decision, head);
-        case 8: return states_step_launch<8>(c, decision, head);
-        case 32: return states_step_launch<32>(c, decision, head);
-        case 64: return states_step_launch<64>(c, decision, head);
-        case 128: return states_step_launch<128>(c, decision, head);
-        default: return MVN_E_STATES;
-    }
+    return dispatch_step_states(c.S, MVN_E_STATES, [&](auto sc) { return states_step_launch<decltype(sc)::value>(c, decision, head); });
 }
 
 }  // namespace
