@@ -267,6 +267,15 @@ __device__ __forceinline__ void hv_chunk(const float *p, const float *v, float *
     }
 }
 
+// ---- pieces of the meta-learning kernels' frame (maml_train_kernel, maml_train_states, maml_train_groups_kernel)
+// sample n of a step's support set (W words of T samples) / of its query word
+struct MetaSamples {
+    const int *__restrict__ support_idx, *__restrict__ query_idx;
+    int W, T;
+    __device__ __forceinline__ long long support(int step, int n) const { return (long long)support_idx[(long long)step * W + n / T] * T + n % T; }
+    __device__ __forceinline__ long long query(int step, int n) const { return (long long)query_idx[step] * T + n; }
+};
+
 template <int SC, bool MANY>  // as online_train_kernel: compile-time n_states or 0 = run-time S_rt; one trial by value or trial blockIdx.y
 __global__ __launch_bounds__(kTrainThreads) void maml_train_kernel(
     const mvn_train_trial_t one, const mvn_train_trial_t *__restrict__ many, int T, int W, float meta_lr, int second_order,
@@ -290,9 +299,7 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_kernel(
     const HvArena<kHvRows> HA(thp);  // ... so the Hessian pass's 32-sample images start there (they need the room)
     const int tid = threadIdx.x;
 
-    for (int e = tid; e < lds_floats; e += kTrainThreads) smem[e] = 0.0f;  // finite everywhere (see online_train_kernel)
-    __syncthreads();
-    load_params(th, L, S, d.w_in);
+    MVN_CLEAR_LDS_LOAD_PARAMS(kTrainThreads, th);
     __syncthreads();
 
     const int n_sup = W * T, n_qry = T;
@@ -324,17 +331,11 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_kernel(
             }
         __syncthreads();
     };
-    // sample n of the step's support set / query word
-    auto support_sample = [&](int step, int n) { return (long long)support_idx[(long long)step * W + n / T] * T + n % T; };
-    auto query_sample = [&](int step, int n) { return (long long)query_idx[step] * T + n; };
+    const MetaSamples smp = {support_idx, query_idx, W, T};
 
     for (int step = 0; step < n_steps; ++step) {
-        auto bias_corrections = [&]() {  // in double like torch's Python side; read by everyone at the Adam update
-            b1pow *= (double)beta1;
-            b2pow *= (double)beta2;
-            A.red[kTrainChunk + 1] = (float)((double)lr / (1.0 - b1pow));
-            A.red[kTrainChunk + 2] = (float)(1.0 / sqrt(1.0 - b2pow));
-        };
+        // (read by everyone at the Adam update)
+        auto bias_corrections = [&]() { next_bias_corrections<true>(b1pow, b2pow, lr, beta1, beta2, A.red[kTrainChunk + 1], A.red[kTrainChunk + 2]); };
         // ---- pass 0: g_s = grad L_support(theta);  pass 1: g_q = grad L_query(theta'), theta' = theta - meta_lr g_s.
         // ONE loop over the two passes and the SAME two LDS vectors in both -- the parameters the pass differentiates at in `th`,
         // its gradient in `ga` -- so that the chunk code (the bulk of the kernel) is inlined once per form with every LDS address
@@ -358,7 +359,7 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_kernel(
                 const int nc = n_pass - c0 < kTrainChunk ? n_pass - c0 : kTrainChunk;
                 if (tid < kTrainChunk) {
                     const bool valid = tid < nc;
-                    const long long s = !valid ? 0 : pass ? query_sample(step, c0 + tid) : support_sample(step, c0 + tid);
+                    const long long s = !valid ? 0 : pass ? smp.query(step, c0 + tid) : smp.support(step, c0 + tid);
                     A.ys[tid] = valid ? rx_words[s] : 0.0f;
                     A.lab[tid] = valid ? labels[s] : 0;
                 }
@@ -387,7 +388,7 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_kernel(
                 const int nc = n_sup - c0 < kHvRows ? n_sup - c0 : kHvRows;
                 if (tid < kHvRows) {
                     const bool valid = tid < nc;
-                    const long long s = valid ? support_sample(step, c0 + tid) : 0;
+                    const long long s = valid ? smp.support(step, c0 + tid) : 0;
                     HA.ys[tid] = valid ? rx_words[s] : 0.0f;
                     HA.lab[tid] = valid ? labels[s] : 0;
                 }
@@ -687,9 +688,7 @@ __device__ __forceinline__ void maml_train_states(const mvn_train_trial_t &d, in
     const float *const w_wait[6] = {d.w_out[0], d.w_out[1], d.w_out[2], d.w_out[3], d.w_out[4], d.w_out[5]};  // where theta waits
     const int tid = threadIdx.x;
 
-    for (int e = tid; e < lds_floats; e += kTrainThreads) smem[e] = 0.0f;  // finite everywhere (see online_train_kernel)
-    __syncthreads();
-    load_params(th, L, S, d.w_in);
+    MVN_CLEAR_LDS_LOAD_PARAMS(kTrainThreads, th);
     __syncthreads();
 
     const int n_sup = W * T, n_qry = T;
@@ -714,16 +713,11 @@ __device__ __forceinline__ void maml_train_states(const mvn_train_trial_t &d, in
         }
         __syncthreads();
     };
-    auto support_sample = [&](int step, int n) { return (long long)support_idx[(long long)step * W + n / T] * T + n % T; };
-    auto query_sample = [&](int step, int n) { return (long long)query_idx[step] * T + n; };
+    const MetaSamples smp = {support_idx, query_idx, W, T};
 
     for (int step = 0; step < n_steps; ++step) {
-        auto bias_corrections = [&]() {  // in double like torch's Python side; read by everyone at the Adam update
-            b1pow *= (double)beta1;
-            b2pow *= (double)beta2;
-            A.red[kTrainChunk + 1] = (float)((double)lr / (1.0 - b1pow));
-            A.red[kTrainChunk + 2] = (float)(1.0 / sqrt(1.0 - b2pow));
-        };
+        // (read by everyone at the Adam update)
+        auto bias_corrections = [&]() { next_bias_corrections<true>(b1pow, b2pow, lr, beta1, beta2, A.red[kTrainChunk + 1], A.red[kTrainChunk + 2]); };
         // ---- pass 0: g_s = grad L_support(theta);  pass 1: g_q = grad L_query(theta'): one loop, the same two vectors (as above)
         clear_pads_grad();
         for (int pass = 0; pass < 2; ++pass) {
@@ -740,7 +734,7 @@ __device__ __forceinline__ void maml_train_states(const mvn_train_trial_t &d, in
                 const int nc = n_pass - c0 < kTrainChunk ? n_pass - c0 : kTrainChunk;
                 if (tid < kTrainChunk) {
                     const bool valid = tid < nc;
-                    const long long s = !valid ? 0 : pass ? query_sample(step, c0 + tid) : support_sample(step, c0 + tid);
+                    const long long s = !valid ? 0 : pass ? smp.query(step, c0 + tid) : smp.support(step, c0 + tid);
                     A.ys[tid] = valid ? rx_words[s] : 0.0f;
                     A.lab[tid] = valid ? labels[s] : 0;
                 }
@@ -768,7 +762,7 @@ __device__ __forceinline__ void maml_train_states(const mvn_train_trial_t &d, in
                 const int nc = n_sup - c0 < kHvRowsStates ? n_sup - c0 : kHvRowsStates;
                 if (tid < kHvRowsStates) {
                     const bool valid = tid < nc;
-                    const long long s = valid ? support_sample(step, c0 + tid) : 0;
+                    const long long s = valid ? smp.support(step, c0 + tid) : 0;
                     HA.ys[tid] = valid ? rx_words[s] : 0.0f;
                     HA.lab[tid] = valid ? labels[s] : 0;
                 }

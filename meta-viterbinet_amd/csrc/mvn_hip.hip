@@ -1029,36 +1029,6 @@ hipError_t clear_group_syncs(float *workspace, size_t stride_floats, int trials,
     return hipMemset2DAsync(workspace, stride_floats * sizeof(float), 0, sizeof(GroupSync), (size_t)trials, st);
 }
 
-template <class Launch>  // launch(SC tag): picks the instantiation for S
-int dispatch_states(int S, bool many, Launch launch) {
-    if (S == 16) return launch(std::integral_constant<int, 16>{});
-    if (S == 32 && !many) return launch(std::integral_constant<int, 32>{});  // (R trials at S = 32 take the run-time form)
-    if (S == 64) return launch(std::integral_constant<int, 64>{});   // } the single-workgroup forms of one trial (online_train_kernel,
-    if (S == 128) return launch(std::integral_constant<int, 128>{}); // } maml_train_kernel <64 | 128, false>)
-    return launch(std::integral_constant<int, 0>{});
-}
-
-// Workgroups per trial a training call runs with (0 = one workgroup per trial): ONE decision function for the launchers and
-// for mvn_vnet_train_kernel_name, so that the form a test or a profile is told is the form that runs.  `many`: the
-// trial-batched entry points (R trials); has_workspace / workspace_bytes as the caller passed them.
-int plan_online_groups(bool many, int R, int T, int M, int S, bool has_workspace, size_t workspace_bytes) {
-    const int groups = M > 0 || S > 32 ? 0 : online_groups(T);  // minibatch iterations are one chunk: nothing to spread; 64 / 128 states: one workgroup
-    const int cus = current_device_cus();
-    if (groups < 2 || !has_workspace || sw(SW_TRAIN_GROUPS) == '0' || groups > cus) return 0;
-    if (workspace_bytes < (many ? (size_t)R * trial_workspace_floats(S, groups) * sizeof(float) : train_groups_workspace_bytes(S, groups)))
-        return 0;
-    if (many && sw(SW_TRAIN_GROUPS) != '1' && one_workgroup_per_trial_is_faster(R, groups, cus, 3.1)) return 0;
-    return groups;
-}
-int plan_maml_groups(bool many, int R, int T, int W, int second_order, int S, bool has_workspace, size_t workspace_bytes) {
-    const int groups = S > 32 ? 0 : maml_groups(T, W, second_order);  // one workgroup per chunk of the largest pass; 64 / 128 states: one workgroup
-    const int cus = current_device_cus();
-    if (groups < 2 || !has_workspace || sw(SW_TRAIN_GROUPS) == '0' || groups > cus) return 0;
-    if (workspace_bytes < (many ? (size_t)R * trial_workspace_floats(S, groups) * sizeof(float) : maml_groups_workspace_bytes(S, groups)))
-        return 0;
-    if (many && sw(SW_TRAIN_GROUPS) != '1' && one_workgroup_per_trial_is_faster(R, groups, cus, second_order ? 3.4 : 3.1)) return 0;
-    return groups;
-}
 
 // More trials than CUs on one workgroup per trial: the 512-thread form of online_train_kernel puts TWO trials on a CU at once
 // (online_train.inc); it needs parameters + gradient + a compact arena within half a CU's LDS (n_states <= 16).  Measured
@@ -1077,118 +1047,151 @@ bool online_pair_form(bool many, int R, int M, int S) {
     return M == 0 && R > current_device_cus();
 }
 
-int launch_online_train(const mvn_train_trial_t &one, const mvn_train_trial_t *many, int R, int T, int M, float lr, float beta1,
-                        float beta2, float eps, int S, void *workspace, size_t workspace_bytes, hipStream_t st) {
-    const size_t lds = online_train_lds_bytes(S);
-    const int lds_floats = (int)online_train_lds_floats(S);
-    const int groups = plan_online_groups(many != nullptr, R, T, M, S, workspace != nullptr, workspace_bytes);
+// How a training call runs: ONE decision function for the launcher and for mvn_vnet_train_kernel_name, which only formats it, so
+// that the form a test or a profile is told is the form that runs.
+enum TrainForm { kTrainPerTrial, kTrainPair, kTrainChunked };  // one workgroup per trial (1024 threads; 512, two per CU) or per chunk
+struct TrainPlan {
+    TrainForm form;
+    int groups;        // workgroups per trial (0 unless chunked)
+    int sc;            // the kernels' template state constant (dispatch_states)
+    int per_launch;    // trials per launch
+    int launches;
+    bool xcd;          // chunked: the XCD-aware grid
+    size_t lds;        // dynamic LDS bytes
+    int lds_floats;
+    size_t stride;     // chunked: floats between the workspace regions of consecutive trials
+    unsigned ws_bytes; // chunked: bytes of one trial's region
+};
+// kind: 0 online (M_or_W = M), 1 / 2 first- / second-order meta-learning (M_or_W = W).  `many`: the trial-batched entry points
+// (R trials; R = 1 otherwise); has_workspace / workspace_bytes as the caller passed them.
+TrainPlan plan_train(int kind, bool many, int R, int T, int M_or_W, int S, bool has_workspace, size_t workspace_bytes) {
+    TrainPlan p = {};
+    // compile-time state counts: 16; 32 for one trial (R trials at S = 32 take the run-time form); 64 / 128, the single-workgroup
+    // forms of one trial (online_train_kernel, maml_train_kernel <64 | 128, false>); 0 = run-time
+    p.sc = S == 16 || (S == 32 && !many) || S == 64 || S == 128 ? S : 0;
+    // one workgroup per chunk of the largest pass.  Minibatch iterations are one chunk: nothing to spread; 64 / 128 states: one workgroup
+    int groups = S > 32 ? 0 : kind == 0 ? (M_or_W > 0 ? 0 : online_groups(T)) : maml_groups(T, M_or_W, kind == 2);
     const int cus = current_device_cus();
-    const size_t stride = groups >= 2 ? trial_workspace_floats(S, groups) : 0;
-    if (groups && (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
-    if (!groups) {  // one workgroup per trial
-        return dispatch_states(S, many != nullptr, [&](auto sc) -> int {
-            constexpr int SC = decltype(sc)::value;
-            if (many && online_pair_form(true, R, M, S)) {  // (16 states only)
-                constexpr int SC2 = SC >= 32 ? 0 : SC;
-                const size_t lds2 = online_train2_lds_bytes(S);
-                if (int e = ensure_dynamic_lds((const void *)online_train_kernel<SC2, true, kTrainThreads2>, lds2)) return e;
-                hipLaunchKernelGGL((online_train_kernel<SC2, true, kTrainThreads2>), dim3(1, (unsigned)R), dim3(kTrainThreads2),
-                                   lds2, st, one, many, T, M, lr, beta1, beta2, eps, S, (int)online_train2_lds_floats(S));
-            } else if (many) {
-                if (int e = ensure_dynamic_lds((const void *)online_train_kernel<SC == 32 ? 0 : SC, true>, lds)) return e;
-                hipLaunchKernelGGL((online_train_kernel<SC == 32 ? 0 : SC, true>), dim3(1, (unsigned)R), dim3(kTrainThreads), lds, st,
-                                   one, many, T, M, lr, beta1, beta2, eps, S, lds_floats);
-            } else {
-                if (int e = ensure_dynamic_lds((const void *)online_train_kernel<SC, false>, lds)) return e;
-                hipLaunchKernelGGL((online_train_kernel<SC, false>), dim3(1), dim3(kTrainThreads), lds, st, one, many, T, M, lr,
-                                   beta1, beta2, eps, S, lds_floats);
-            }
-            return (int)hipGetLastError();
-        });
+    if (groups < 2 || !has_workspace || sw(SW_TRAIN_GROUPS) == '0' || groups > cus) groups = 0;
+    const size_t need_one = !groups ? 0 : kind == 0 ? train_groups_workspace_bytes(S, groups) : maml_groups_workspace_bytes(S, groups);
+    const size_t stride = groups ? trial_workspace_floats(S, groups) : 0;
+    if (workspace_bytes < (many ? (size_t)R * stride * sizeof(float) : need_one)) groups = 0;
+    // (a second-order step is 3.4 x as long on one CU as on its chunks' CUs, the others 3.1 x: one_workgroup_per_trial_is_faster)
+    if (many && sw(SW_TRAIN_GROUPS) != '1' && one_workgroup_per_trial_is_faster(R, groups, cus, kind == 2 ? 3.4 : 3.1)) groups = 0;
+    p.groups = groups;
+    p.form = groups ? kTrainChunked : kind == 0 && online_pair_form(many, R, M_or_W, S) ? kTrainPair : kTrainPerTrial;
+    p.lds_floats = (int)(p.form == kTrainPair ? online_train2_lds_floats(S) : kind == 0 ? online_train_lds_floats(S) : maml_train_lds_floats(S));
+    p.lds = (size_t)p.lds_floats * sizeof(float);
+    p.per_launch = R;  // one workgroup per trial: one launch
+    if (groups) {  // never more workgroups in a launch than the device has CUs (all resident at once)
+        p.xcd = xcd_grid(groups, cus, R, many);
+        p.per_launch = many ? trials_per_launch(R, group_trials_fit(groups, cus, R)) : 1;
+        p.stride = stride;
+        p.ws_bytes = (unsigned)(many ? stride * sizeof(float) : need_one);
     }
-    // one workgroup per chunk and trial, never more workgroups in a launch than the device has CUs (all resident at once)
-    const size_t ws_floats_one = train_groups_workspace_bytes(S, groups) / sizeof(float);
-    const bool xcd = xcd_grid(groups, cus, R, many != nullptr);
-    const int per_launch = many ? trials_per_launch(R, group_trials_fit(groups, cus, R)) : 1;
-    for (int r0 = 0; r0 < R; r0 += per_launch) {
-        const int nr = std::min(per_launch, R - r0);
-        float *wsr = (float *)workspace + (size_t)r0 * stride;
-        hipError_t e = clear_group_syncs(wsr, stride, nr, st);
+    p.launches = (R + p.per_launch - 1) / p.per_launch;
+    return p;
+}
+
+template <class Launch>  // launch(SC tag): picks the instantiation for the plan's state constant
+int dispatch_states(int sc, Launch launch) {
+    if (sc == 16) return launch(std::integral_constant<int, 16>{});
+    if (sc == 32) return launch(std::integral_constant<int, 32>{});
+    if (sc == 64) return launch(std::integral_constant<int, 64>{});
+    if (sc == 128) return launch(std::integral_constant<int, 128>{});
+    return launch(std::integral_constant<int, 0>{});
+}
+
+// One launch of a training kernel, its dynamic-LDS limit raised first.  args: the kernel's, in order.
+template <class... P, class Args>
+int train_launch(void (*kernel)(P...), dim3 grid, unsigned threads, const TrainPlan &p, hipStream_t st, const Args &args) {
+    if (int e = ensure_dynamic_lds((const void *)kernel, p.lds)) return e;
+    std::apply([&](auto... a) { hipLaunchKernelGGL(kernel, grid, dim3(threads), p.lds, st, a...); }, args);
+    return (int)hipGetLastError();
+}
+
+// What the launches of a training call share.  A kernel's arguments are (one, many, `mid`..., S, lds_floats[, GroupLaunch]).
+struct TrainCall {
+    TrainPlan plan;
+    const mvn_train_trial_t &one;
+    const mvn_train_trial_t *many;
+    int R, S;
+    void *workspace;
+    hipStream_t st;
+};
+// one workgroup per trial: all trials in one launch
+template <class... P, class Mid>
+int train_run(void (*k_many)(P...), void (*k_one)(P...), const TrainCall &c, unsigned threads, const Mid &mid) {
+    return train_launch(c.many ? k_many : k_one, c.many ? dim3(1, (unsigned)c.R) : dim3(1), threads, c.plan, c.st,
+                        std::tuple_cat(std::make_tuple(c.one, c.many), mid, std::make_tuple(c.S, c.plan.lds_floats)));
+}
+// one workgroup per chunk and trial: R trials, plan.per_launch at a time
+template <class... P, class Mid>
+int train_run_chunked(void (*k_many)(P...), void (*k_one)(P...), const TrainCall &c, const Mid &mid) {
+    const TrainPlan &p = c.plan;
+    for (int r0 = 0; r0 < c.R; r0 += p.per_launch) {
+        const int nr = std::min(p.per_launch, c.R - r0);
+        float *wsr = (float *)c.workspace + (size_t)r0 * p.stride;
+        hipError_t e = clear_group_syncs(wsr, p.stride, nr, c.st);
         if (e != hipSuccess) return (int)e;
-        const GroupLaunch gl = {wsr, (long long)stride, (unsigned)((many ? stride : ws_floats_one) * sizeof(float)), group_spin_limit(), group_phantoms(),
-                                xcd ? groups : 0, nr, next_xcd_slot(xcd, many != nullptr)};
-        const dim3 grid = xcd ? dim3(group_grid_blocks(groups, nr)) : dim3((unsigned)groups, (unsigned)nr);
-        const int rc = dispatch_states(S, many != nullptr, [&](auto sc) -> int {
-            constexpr int SC = decltype(sc)::value > 32 ? 0 : decltype(sc)::value;  // (never above 32 states: plan_online_groups)
-            if (many) {
-                if (int e2 = ensure_dynamic_lds((const void *)online_train_groups_kernel<SC == 32 ? 0 : SC, true>, lds)) return e2;
-                hipLaunchKernelGGL((online_train_groups_kernel<SC == 32 ? 0 : SC, true>), grid,
-                                   dim3(kTrainThreads), lds, st, one, many + r0, T, lr, beta1, beta2, eps, S, lds_floats, gl);
-            } else {
-                if (int e2 = ensure_dynamic_lds((const void *)online_train_groups_kernel<SC, false>, lds)) return e2;
-                hipLaunchKernelGGL((online_train_groups_kernel<SC, false>), grid, dim3(kTrainThreads), lds, st, one,
-                                   many, T, lr, beta1, beta2, eps, S, lds_floats, gl);
-            }
-            return (int)hipGetLastError();
-        });
+        const GroupLaunch gl = {wsr, (long long)p.stride, p.ws_bytes, group_spin_limit(), group_phantoms(),
+                                p.xcd ? p.groups : 0, nr, next_xcd_slot(p.xcd, c.many != nullptr)};
+        const dim3 grid = p.xcd ? dim3(group_grid_blocks(p.groups, nr)) : dim3((unsigned)p.groups, (unsigned)nr);
+        const int rc = train_launch(c.many ? k_many : k_one, grid, kTrainThreads, p, c.st,
+                                    std::tuple_cat(std::make_tuple(c.one, c.many ? c.many + r0 : c.many), mid,
+                                                   std::make_tuple(c.S, p.lds_floats, gl)));
         if (rc) return rc;
     }
     return MVN_OK;
 }
 
-int launch_maml_train(const mvn_train_trial_t &one, const mvn_train_trial_t *many, int R, int T, int W, float meta_lr,
-                      int second_order, float lr, float beta1, float beta2, float eps, int S, void *workspace,
-                      size_t workspace_bytes, hipStream_t st) {
-    const size_t lds = maml_train_lds_floats(S) * sizeof(float);
-    const int lds_floats = (int)maml_train_lds_floats(S);
-    const int groups = plan_maml_groups(many != nullptr, R, T, W, second_order, S, workspace != nullptr, workspace_bytes);
-    const int cus = current_device_cus();
-    const size_t stride = groups >= 2 ? trial_workspace_floats(S, groups) : 0;
-    if (groups && (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
-    if (!groups) {
-        return dispatch_states(S, many != nullptr, [&](auto sc) -> int {
-            constexpr int SC1 = decltype(sc)::value;     // one trial: 64 / 128 states have their own form (maml_train.inc)
-            constexpr int SC = SC1 > 32 ? 0 : SC1;       // R trials: up to 32 states (the entry point refuses more)
-            if (many) {
-                if (int e = ensure_dynamic_lds((const void *)maml_train_kernel<SC == 32 ? 0 : SC, true>, lds)) return e;
-                hipLaunchKernelGGL((maml_train_kernel<SC == 32 ? 0 : SC, true>), dim3(1, (unsigned)R), dim3(kTrainThreads), lds, st, one,
-                                   many, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, lds_floats);
-            } else {
-                if (int e = ensure_dynamic_lds((const void *)maml_train_kernel<SC1, false>, lds)) return e;
-                hipLaunchKernelGGL((maml_train_kernel<SC1, false>), dim3(1), dim3(kTrainThreads), lds, st, one, many, T, W, meta_lr,
-                                   second_order, lr, beta1, beta2, eps, S, lds_floats);
-            }
-            return (int)hipGetLastError();
-        });
-    }
-    const size_t ws_floats_one = maml_groups_workspace_bytes(S, groups) / sizeof(float);
-    const bool xcd = xcd_grid(groups, cus, R, many != nullptr);
-    const int per_launch = many ? trials_per_launch(R, group_trials_fit(groups, cus, R)) : 1;
-    for (int r0 = 0; r0 < R; r0 += per_launch) {
-        const int nr = std::min(per_launch, R - r0);
-        float *wsr = (float *)workspace + (size_t)r0 * stride;
-        hipError_t e = clear_group_syncs(wsr, stride, nr, st);
-        if (e != hipSuccess) return (int)e;
-        const GroupLaunch gl = {wsr, (long long)stride, (unsigned)((many ? stride : ws_floats_one) * sizeof(float)), group_spin_limit(), group_phantoms(),
-                                xcd ? groups : 0, nr, next_xcd_slot(xcd, many != nullptr)};
-        const dim3 grid = xcd ? dim3(group_grid_blocks(groups, nr)) : dim3((unsigned)groups, (unsigned)nr);
-        const int rc = dispatch_states(S, many != nullptr, [&](auto sc) -> int {
-            constexpr int SC = decltype(sc)::value > 32 ? 0 : decltype(sc)::value;  // (never above 32 states: plan_maml_groups)
-            if (many) {
-                if (int e2 = ensure_dynamic_lds((const void *)maml_train_groups_kernel<SC == 32 ? 0 : SC, true>, lds)) return e2;
-                hipLaunchKernelGGL((maml_train_groups_kernel<SC == 32 ? 0 : SC, true>), grid,
-                                   dim3(kTrainThreads), lds, st, one, many + r0, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S,
-                                   lds_floats, gl);
-            } else {
-                if (int e2 = ensure_dynamic_lds((const void *)maml_train_groups_kernel<SC, false>, lds)) return e2;
-                hipLaunchKernelGGL((maml_train_groups_kernel<SC, false>), grid, dim3(kTrainThreads), lds, st, one,
-                                   many, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, lds_floats, gl);
-            }
-            return (int)hipGetLastError();
-        });
-        if (rc) return rc;
-    }
-    return MVN_OK;
+// The online (maml false: M_or_W = M, meta_lr and second_order unused) and the meta-learning trainer, one trial by value or R trials
+int launch_train(bool maml, const mvn_train_trial_t &one, const mvn_train_trial_t *many, int R, int T, int M_or_W, float meta_lr,
+                 int second_order, float lr, float beta1, float beta2, float eps, int S, void *workspace, size_t workspace_bytes,
+                 hipStream_t st) {
+    const TrainCall c = {plan_train(maml ? (second_order ? 2 : 1) : 0, many != nullptr, R, T, M_or_W, S, workspace != nullptr, workspace_bytes),
+                         one, many, R, S, workspace, st};
+    if (c.plan.groups && (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
+    const auto adam = std::make_tuple(lr, beta1, beta2, eps);
+    const auto meta = std::tuple_cat(std::make_tuple(T, M_or_W, meta_lr, second_order), adam);
+    return dispatch_states(c.plan.sc, [&](auto sc) -> int {
+        constexpr int SC1 = decltype(sc)::value;    // one workgroup per trial: 64 / 128 states have their own forms
+        constexpr int SC1M = SC1 == 32 ? 0 : SC1;   // (the run-time form for R trials at 32 states)
+        constexpr int SC = SC1 > 32 ? 0 : SC1;      // the chunked kernels and R meta-learning trials: up to 32 states (plan_train, the entry point)
+        constexpr int SCM = SC == 32 ? 0 : SC;
+        if (c.plan.form == kTrainChunked) {
+            if (maml) return train_run_chunked(maml_train_groups_kernel<SCM, true>, maml_train_groups_kernel<SC, false>, c, meta);
+            return train_run_chunked(online_train_groups_kernel<SCM, true>, online_train_groups_kernel<SC, false>, c,
+                                     std::tuple_cat(std::make_tuple(T), adam));
+        }
+        if (maml) return train_run(maml_train_kernel<SCM, true>, maml_train_kernel<SC1, false>, c, kTrainThreads, meta);
+        const auto online = std::tuple_cat(std::make_tuple(T, M_or_W), adam);
+        if (c.plan.form == kTrainPair) {  // (16 states, R trials only)
+            constexpr auto pair = online_train_kernel<SC1 >= 32 ? 0 : SC1, true, kTrainThreads2>;
+            return train_run(pair, pair, c, kTrainThreads2, online);
+        }
+        return train_run(online_train_kernel<SC1M, true>, online_train_kernel<SC1, false>, c, kTrainThreads, online);
+    });
+}
+
+// the by-value descriptor of the single-trial entry points: weights updated in place, Adam's running powers at step0
+mvn_train_trial_t train_trial(const float *y, const int32_t *labels, const int32_t *idx, const int32_t *query_idx, float *const (&w)[6],
+                              float *adam_m, float *adam_v, float *loss_out, int32_t *status, float beta1, float beta2, int64_t step0,
+                              int32_t n) {
+    mvn_train_trial_t d = {};
+    d.y = y;
+    d.labels = labels;
+    d.idx = idx;
+    d.query_idx = query_idx;
+    for (int a = 0; a < 6; ++a) d.w_in[a] = d.w_out[a] = w[a];
+    d.adam_m = adam_m;
+    d.adam_v = adam_v;
+    d.loss_out = loss_out;
+    d.status = status;
+    d.b1pow = pow((double)beta1, (double)step0);
+    d.b2pow = pow((double)beta2, (double)step0);
+    d.n = n;
+    return d;
 }
 
 // R trials at 64 / 128 states: one workgroup per trial, all of them in ONE launch whatever R is (no workspace, no barrier
@@ -1687,24 +1690,10 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
     if (!valid_states(S) || S > 128) return MVN_E_STATES;  // parameters + gradient + a chunk must fit the 160-KB LDS
     if (n_iter == 0) return MVN_OK;
     if (!y || !labels || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !adam_m || !adam_v) return MVN_E_NULL;
-    mvn_train_trial_t d = {};
-    d.y = y;
-    d.labels = labels;
-    d.idx = batch_idx;
-    float *w[6] = {W1, b1, W2, b2, W3, b3};
-    for (int a = 0; a < 6; ++a) {
-        d.w_in[a] = w[a];
-        d.w_out[a] = w[a];
-    }
-    d.adam_m = adam_m;
-    d.adam_v = adam_v;
-    d.loss_out = loss_out;
-    d.status = status;
-    d.b1pow = pow((double)beta1, (double)step0);
-    d.b2pow = pow((double)beta2, (double)step0);
-    d.n = n_iter;
-    return launch_online_train(d, nullptr, 1, T, batch_idx ? M : 0, lr, beta1, beta2, eps, S, workspace, workspace_bytes,
-                               (hipStream_t)stream);
+    const mvn_train_trial_t d = train_trial(y, labels, batch_idx, nullptr, {W1, b1, W2, b2, W3, b3}, adam_m, adam_v, loss_out, status,
+                                            beta1, beta2, step0, n_iter);
+    return launch_train(false, d, nullptr, 1, T, batch_idx ? M : 0, 0.0f, 0, lr, beta1, beta2, eps, S, workspace, workspace_bytes,
+                        (hipStream_t)stream);
 }
 
 size_t mvn_vnet_train_lds_bytes(int32_t kind, int32_t S) {
@@ -1719,8 +1708,8 @@ int mvn_vnet_online_train_trials_f32(const mvn_train_trial_t *trials, int32_t R,
     if (!valid_states(S) || S > 128) return MVN_E_STATES;
     if (R == 0) return MVN_OK;
     if (!trials) return MVN_E_NULL;
-    return launch_online_train(mvn_train_trial_t{}, trials, R, T, M, lr, beta1, beta2, eps, S, workspace, workspace_bytes,
-                               (hipStream_t)stream);
+    return launch_train(false, mvn_train_trial_t{}, trials, R, T, M, 0.0f, 0, lr, beta1, beta2, eps, S, workspace, workspace_bytes,
+                        (hipStream_t)stream);
 }
 
 int mvn_vnet_maml_train_f32(const float *rx_words, const int32_t *labels, int32_t T, const int32_t *support_idx, int32_t W,
@@ -1745,25 +1734,10 @@ int mvn_vnet_maml_train_ws_f32(const float *rx_words, const int32_t *labels, int
     if (n_steps == 0) return MVN_OK;
     if (!rx_words || !labels || !support_idx || !query_idx || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !adam_m || !adam_v)
         return MVN_E_NULL;
-    mvn_train_trial_t d = {};
-    d.y = rx_words;
-    d.labels = labels;
-    d.idx = support_idx;
-    d.query_idx = query_idx;
-    float *w[6] = {W1, b1, W2, b2, W3, b3};
-    for (int a = 0; a < 6; ++a) {
-        d.w_in[a] = w[a];
-        d.w_out[a] = w[a];
-    }
-    d.adam_m = adam_m;
-    d.adam_v = adam_v;
-    d.loss_out = loss_out;
-    d.status = status;
-    d.b1pow = pow((double)beta1, (double)step0);
-    d.b2pow = pow((double)beta2, (double)step0);
-    d.n = n_steps;
-    return launch_maml_train(d, nullptr, 1, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, workspace, workspace_bytes,
-                             (hipStream_t)stream);
+    const mvn_train_trial_t d = train_trial(rx_words, labels, support_idx, query_idx, {W1, b1, W2, b2, W3, b3}, adam_m, adam_v, loss_out,
+                                            status, beta1, beta2, step0, n_steps);
+    return launch_train(true, d, nullptr, 1, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, workspace, workspace_bytes,
+                        (hipStream_t)stream);
 }
 
 int mvn_vnet_maml_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t W, float meta_lr,
@@ -1773,8 +1747,8 @@ int mvn_vnet_maml_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, i
     if (!valid_states(S) || S > 32) return MVN_E_STATES;
     if (R == 0) return MVN_OK;
     if (!trials) return MVN_E_NULL;
-    return launch_maml_train(mvn_train_trial_t{}, trials, R, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, workspace,
-                             workspace_bytes, (hipStream_t)stream);
+    return launch_train(true, mvn_train_trial_t{}, trials, R, T, W, meta_lr, second_order, lr, beta1, beta2, eps, S, workspace,
+                        workspace_bytes, (hipStream_t)stream);
 }
 
 int mvn_vnet_maml_train_states_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t W, float meta_lr,
@@ -1795,25 +1769,18 @@ int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_
     if (!valid_states(S) || S > 128 || (kind > 0 && R > 0 && S > 32)) return MVN_E_STATES;
     if (!name || name_len < 1) return MVN_E_NULL;
     const bool many = R > 0;
-    const int n_trials = many ? R : 1;
-    const int groups = kind == 0 ? plan_online_groups(many, n_trials, T, M_or_W, S, workspace_bytes > 0, workspace_bytes)
-                                 : plan_maml_groups(many, n_trials, T, M_or_W, kind == 2, S, workspace_bytes > 0, workspace_bytes);
-    const int sc = S == 16 ? 16 : (S == 32 && !many) ? 32 : S > 32 ? S : 0;  // dispatch_states
-    const char *base = kind == 0 ? "online_train" : "maml_train";
-    if (!groups && kind == 0 && online_pair_form(many, n_trials, M_or_W, S)) {
-        snprintf(name, (size_t)name_len, "%s_kernel<%d, true, %d> 1x%d", base, sc, kTrainThreads2, n_trials);
-    } else if (!groups) {
-        snprintf(name, (size_t)name_len, "%s_kernel<%d, %s> 1x%d", base, sc, many ? "true" : "false", n_trials);
-    } else {
-        const int per_launch = many ? trials_per_launch(n_trials, group_trials_fit(groups, current_device_cus(), n_trials)) : 1;
-        const int launches = (n_trials + per_launch - 1) / per_launch;
-        const char *place = xcd_grid(groups, current_device_cus(), n_trials, many) ? " one XCD per trial" : "";
-        if (launches > 1)
-            snprintf(name, (size_t)name_len, "%s_groups_kernel<%d, %s> %dx%d in %d launches%s", base, sc, many ? "true" : "false", groups,
-                     per_launch, launches, place);
-        else
-            snprintf(name, (size_t)name_len, "%s_groups_kernel<%d, %s> %dx%d%s", base, sc, many ? "true" : "false", groups, per_launch, place);
-    }
+    const TrainPlan p = plan_train(kind, many, many ? R : 1, T, M_or_W, S, workspace_bytes > 0, workspace_bytes);
+    const char *base = kind == 0 ? "online_train" : "maml_train", *trials = many ? "true" : "false";
+    const size_t len = (size_t)name_len;
+    if (p.form == kTrainPair)
+        snprintf(name, len, "%s_kernel<%d, true, %d> 1x%d", base, p.sc, kTrainThreads2, p.per_launch);
+    else if (p.form == kTrainPerTrial)
+        snprintf(name, len, "%s_kernel<%d, %s> 1x%d", base, p.sc, trials, p.per_launch);
+    else if (p.launches > 1)
+        snprintf(name, len, "%s_groups_kernel<%d, %s> %dx%d in %d launches%s", base, p.sc, trials, p.groups, p.per_launch, p.launches,
+                 p.xcd ? " one XCD per trial" : "");
+    else
+        snprintf(name, len, "%s_groups_kernel<%d, %s> %dx%d%s", base, p.sc, trials, p.groups, p.per_launch, p.xcd ? " one XCD per trial" : "");
     return MVN_OK;
 }
 

@@ -698,6 +698,46 @@ __device__ __forceinline__ void store_trial_params(const float *p, const TrainLa
     if (d.w_out2[0]) store_params<NT>(p, L, S, d.w_out2);
 }
 
+// ---- the frame the training kernels share around grad_chunk / hv_chunk.  A piece is shared only in a form that leaves the disassembly
+// of every training kernel as it was (tools/kernel_isa_diff.py): a function where that holds, else a text, and what changes code
+// either way stays duplicated (the clear_pads_* lambdas of the meta-learning kernels; profiles/train_isa_identity.txt).
+// Every float the tile products can touch must be finite: clear the whole allocation first (padding columns and the operand rows
+// read past a matrix edge stay zero or hold live finite data afterwards), then stage the parameters `p` of trial `d`.
+// (A text: as a function it changes maml_train_kernel.)
+#define MVN_CLEAR_LDS_LOAD_PARAMS(NT, p)                           \
+    do {                                                           \
+        for (int e = tid; e < lds_floats; e += NT) smem[e] = 0.0f; \
+        __syncthreads();                                           \
+        load_params<NT>(p, L, S, d.w_in);                          \
+    } while (0)
+
+// Adam's moments (flat torch order in global memory) into / out of the LDS vectors
+template <int NT = kTrainThreads>
+__device__ __forceinline__ void moments_to_lds(float *am, float *av, const float *adam_m, const float *adam_v, int Pflat, int tid) {
+    for (int e = tid; e < Pflat; e += NT) {
+        am[lds_index(e)] = adam_m[e];
+        av[lds_index(e)] = adam_v[e];
+    }
+}
+template <int NT = kTrainThreads>
+__device__ __forceinline__ void moments_from_lds(const float *am, const float *av, float *adam_m, float *adam_v, int Pflat, int tid) {
+    for (int e = tid; e < Pflat; e += NT) {
+        adam_m[e] = am[lds_index(e)];
+        adam_v[e] = av[lds_index(e)];
+    }
+}
+
+// Adam's bias corrections of the next step, in double like torch's Python side: advances the running powers.  ADAM_ONLY: the
+// meta-learning kernels (their entry points refuse the RMSprop / SGD tags) spell the step size out.
+template <bool ADAM_ONLY>
+__device__ __forceinline__ void next_bias_corrections(double &b1pow, double &b2pow, float lr, float beta1, float beta2, float &step_size,
+                                                      float &inv_sqrt_bc2) {
+    b1pow *= (double)beta1;
+    b2pow *= (double)beta2;
+    step_size = ADAM_ONLY ? (float)((double)lr / (1.0 - b1pow)) : train_step_size(lr, beta1, b1pow);
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - b2pow));
+}
+
 // SC: n_states as a compile-time constant (16, 32: every LDS offset becomes an immediate) or 0 = run-time S_rt (any S <= 32).
 // MANY = false: the trial is the by-value argument `one` (the single-trial entry points); true: trial blockIdx.y of the
 // device array `many` (mvn_vnet_online_train_trials_f32), a trial with n = 0 exits at once.
@@ -733,16 +773,8 @@ __global__ __launch_bounds__(NT, NT == kTrainThreads ? 1 : 4) void online_train_
     const ChunkArena<kTrainChunk> A(kMomentsInLds ? av + L.P4 : g + L.P4, NT != kTrainThreads, SCC ? SCC + 2 : kDlStride);
     const int tid = threadIdx.x;
 
-    // Every float the tile products can touch must be finite: clear the whole allocation first (padding columns and
-    // the operand rows read past a matrix edge stay zero or hold live finite data afterwards).
-    for (int e = tid; e < lds_floats; e += NT) smem[e] = 0.0f;
-    __syncthreads();
-    load_params<NT>(p, L, S, d.w_in);
-    if (kMomentsInLds)
-        for (int e = tid; e < L.Pflat; e += NT) {
-            am[lds_index(e)] = adam_m[e];
-            av[lds_index(e)] = adam_v[e];
-        }
+    MVN_CLEAR_LDS_LOAD_PARAMS(NT, p);
+    if (kMomentsInLds) moments_to_lds<NT>(am, av, adam_m, adam_v, L.Pflat, tid);
     __syncthreads();
 
     const int n_total = batch_idx ? M : T;  // samples per iteration
@@ -793,12 +825,7 @@ __global__ __launch_bounds__(NT, NT == kTrainThreads ? 1 : 4) void online_train_
         if (tid == NT - 1) A.red[kTrainChunk] = 0.0f;  // running loss of this iteration
         // Adam's bias corrections in double like torch's Python side, by one lane of the last wave while it idles in
         // the first chunk's first matrix product; everyone reads them after the barriers in between
-        auto bias_corrections = [&]() {
-            b1pow *= (double)beta1;
-            b2pow *= (double)beta2;
-            A.red[kTrainChunk + 1] = train_step_size(lr, beta1, b1pow);
-            A.red[kTrainChunk + 2] = (float)(1.0 / sqrt(1.0 - b2pow));
-        };
+        auto bias_corrections = [&]() { next_bias_corrections<false>(b1pow, b2pow, lr, beta1, beta2, A.red[kTrainChunk + 1], A.red[kTrainChunk + 2]); };
         // three inlined copies of the chunk code (it is the bulk of the kernel; the instruction cache holds 64 KB): the pass's
         // first chunk, a further full chunk, a further chunk of at most 16 samples
         for (int c0 = 0; c0 < n_total; c0 += kTrainChunk) {
@@ -867,11 +894,7 @@ __global__ __launch_bounds__(NT, NT == kTrainThreads ? 1 : 4) void online_train_
 #endif
 
     store_trial_params<NT>(p, L, S, d);
-    if (kMomentsInLds)
-        for (int e = tid; e < L.Pflat; e += NT) {
-            adam_m[e] = am[lds_index(e)];
-            adam_v[e] = av[lds_index(e)];
-        }
+    if (kMomentsInLds) moments_from_lds<NT>(am, av, adam_m, adam_v, L.Pflat, tid);
 }
 
 inline size_t online_train_lds_floats(int S) {

@@ -278,6 +278,20 @@ __device__ __forceinline__ void set_same_xcd(SlotIO &io, GroupSync *gs, bool goo
     __syncthreads();
     io.same_xcd = same != 0;
 }
+// Workgroup 0 of a trial after its last step, parameters in `p`.  ANY workgroup of the trial may have given up a wait (it then read
+// incomplete slots while this one passed its barriers late but complete): the trial's failed flag decides, not only this workgroup's
+// own waits.  A barrier was abandoned: make it impossible to miss (NaN weights) and tell the caller (status word).
+// (A text: as a function it changes every chunked kernel.)
+#define MVN_FINISH_GROUP_TRIAL(p)                                                              \
+    do {                                                                                       \
+        good = good && !trial_failed(gs);                                                      \
+        if (!good) {                                                                           \
+            for (int e = tid; e < L.P4; e += kTrainThreads) p[e] = __int_as_float(0x7fc00000); \
+            if (tid == 0 && d.status) *d.status = 1;                                           \
+        }                                                                                      \
+        __syncthreads();                                                                       \
+        store_trial_params(p, L, S, d);                                                        \
+    } while (0)
 
 // online_train_kernel's full-word mode (batch_idx == NULL), gridDim.x = ceil(T / 32) workgroups, workgroup w = chunk w,
 // gridDim.y = trials (MANY) or 1
@@ -309,13 +323,8 @@ __global__ __launch_bounds__(kTrainThreads) void online_train_groups_kernel(
     const bool skip_tag = gl.phantoms < 0 && w == -gl.phantoms - 1;  // test hook: this workgroup never publishes its tag
 
     announce_xcd(gs);
-    for (int e = tid; e < lds_floats; e += kTrainThreads) smem[e] = 0.0f;
-    __syncthreads();
-    load_params(p, L, S, d.w_in);
-    for (int e = tid; e < L.Pflat; e += kTrainThreads) {
-        am[lds_index(e)] = adam_m[e];
-        av[lds_index(e)] = adam_v[e];
-    }
+    MVN_CLEAR_LDS_LOAD_PARAMS(kTrainThreads, p);
+    moments_to_lds(am, av, adam_m, adam_v, L.Pflat, tid);
     const int c0 = w * kTrainChunk;
     const int nc = T - c0 < kTrainChunk ? T - c0 : kTrainChunk;
     if (tid < kTrainChunk) {  // the chunk is the same in every iteration
@@ -333,12 +342,8 @@ __global__ __launch_bounds__(kTrainThreads) void online_train_groups_kernel(
     }
     for (int it = 0; it < n_iter && good; ++it) {
         if (tid == kTrainThreads - 1) A.red[kTrainChunk] = 0.0f;
-        auto bias_corrections = [&]() {  // every workgroup keeps its own (identical) running powers
-            b1pow *= (double)beta1;
-            b2pow *= (double)beta2;
-            A.red[kTrainChunk + 1] = train_step_size(lr, beta1, b1pow);
-            A.red[kTrainChunk + 2] = (float)(1.0 / sqrt(1.0 - b2pow));
-        };
+        // (every workgroup keeps its own, identical, running powers)
+        auto bias_corrections = [&]() { next_bias_corrections<false>(b1pow, b2pow, lr, beta1, beta2, A.red[kTrainChunk + 1], A.red[kTrainChunk + 2]); };
         // (the word's tail runs the 16-row chunk exactly where online_train_kernel does: chunk 0 is always the full form.  Every
         // workgroup WRITES its own gradient vector; the slots are then summed in chunk order, online_train_kernel's order)
         if (w > 0 && nc <= 16) grad_chunk<16, true>(p, g, L, A, nc, inv_n, S, bias_corrections);
@@ -370,19 +375,8 @@ __global__ __launch_bounds__(kTrainThreads) void online_train_groups_kernel(
         __syncthreads();
     }
     if (w != 0) return;
-    // ANY workgroup of the trial may have given up a wait (it then read incomplete slots while this one passed its barriers
-    // late but complete): the trial's failed flag decides, not only this workgroup's own waits
-    good = good && !trial_failed(gs);
-    if (!good) {  // a barrier was abandoned: make it impossible to miss (NaN weights) and tell the caller (status word)
-        for (int e = tid; e < L.P4; e += kTrainThreads) p[e] = __int_as_float(0x7fc00000);
-        if (tid == 0 && d.status) *d.status = 1;
-    }
-    __syncthreads();
-    store_trial_params(p, L, S, d);
-    for (int e = tid; e < L.Pflat; e += kTrainThreads) {
-        adam_m[e] = am[lds_index(e)];
-        adam_v[e] = av[lds_index(e)];
-    }
+    MVN_FINISH_GROUP_TRIAL(p);
+    moments_from_lds(am, av, adam_m, adam_v, L.Pflat, tid);
 }
 
 // maml_train_kernel with one workgroup per chunk of a pass: gridDim.x = the largest chunk count of the three passes
@@ -424,9 +418,7 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_groups_kernel(
     float *mom_m = w == 0 ? adam_m : workspace + slots + (size_t)2 * G * X + (size_t)(w - 1) * 2 * L.Pflat;
     float *mom_v = w == 0 ? adam_v : mom_m + L.Pflat;
 
-    for (int e = tid; e < lds_floats; e += kTrainThreads) smem[e] = 0.0f;
-    __syncthreads();
-    load_params(th, L, S, d.w_in);
+    MVN_CLEAR_LDS_LOAD_PARAMS(kTrainThreads, th);
     if (w != 0)
         for (int e = tid; e < L.Pflat; e += kTrainThreads) {  // thread e owns moment e from here to the end
             mom_m[e] = adam_m[e];
@@ -463,8 +455,7 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_groups_kernel(
                 HA.Rdo[e] = 0.0f;
             }
     };
-    auto support_sample = [&](int step, int n) { return (long long)support_idx[(long long)step * W + n / T] * T + n % T; };
-    auto query_sample = [&](int step, int n) { return (long long)query_idx[step] * T + n; };
+    const MetaSamples smp = {support_idx, query_idx, W, T};
     // this workgroup's vector `vec` (float4 e4 owned by thread e4 after a chunk call) -> its slot of the next exchange
     auto publish = [&](const float *vec, float extra) {
         const size_t mine = slots + ((size_t)(xchg & 1) * G + w) * X;
@@ -489,12 +480,12 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_groups_kernel(
         if (tid < kTrainChunk && step < n_steps) {
             const int ns = w * kTrainChunk + tid;
             if (w < sup_chunks && ns < n_sup) {
-                const long long s_ = support_sample(step, ns);
+                const long long s_ = smp.support(step, ns);
                 r.ys = rx_words[s_];
                 r.labs = labels[s_];
             }
             if (w < qry_chunks && ns < n_qry) {
-                const long long s_ = query_sample(step, ns);
+                const long long s_ = smp.query(step, ns);
                 r.yq = rx_words[s_];
                 r.labs |= labels[s_] << 8;
             }
@@ -509,12 +500,7 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_groups_kernel(
             s_cur_lab[tid] = nxt.labs;
         }
         nxt = fetch_step(step + 1);
-        if (tid == kTrainThreads - 1) {  // Adam's bias corrections in double like torch's Python side
-            b1pow *= (double)beta1;
-            b2pow *= (double)beta2;
-            s_step_size = (float)((double)lr / (1.0 - b1pow));
-            s_inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - b2pow));
-        }
+        if (tid == kTrainThreads - 1) next_bias_corrections<true>(b1pow, b2pow, lr, beta1, beta2, s_step_size, s_inv_sqrt_bc2);
         // ---- pass 0: g_s = grad L_support(theta), chunk w -> slot, theta' = theta - meta_lr sum of the slots;
         //      pass 1: g_q = grad L_query(theta'), chunk w -> slot, sum -> gq.  One loop over the passes with the pass's parameters
         //      always in `th` and its gradient in `ga` (theta waits in `thp` during the query pass): one inlined copy of the chunk
@@ -603,13 +589,7 @@ __global__ __launch_bounds__(kTrainThreads) void maml_train_groups_kernel(
         __syncthreads();
     }
     if (w != 0) return;
-    good = good && !trial_failed(gs);  // (as in online_train_groups_kernel)
-    if (!good) {
-        for (int e = tid; e < L.P4; e += kTrainThreads) th[e] = __int_as_float(0x7fc00000);
-        if (tid == 0 && d.status) *d.status = 1;
-    }
-    __syncthreads();
-    store_trial_params(th, L, S, d);
+    MVN_FINISH_GROUP_TRIAL(th);
 }
 
 inline size_t maml_groups_workspace_bytes(int S, int groups) {
