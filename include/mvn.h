@@ -52,7 +52,7 @@ typedef void *mvn_stream_t; /* hipStream_t */
 
 #define MVN_E_BARRIER (-7)   /* (status words only) a training launch abandoned its device-wide barrier */
 
-#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32, the list steps, mvn_vnet_byword_step_states_f32, mvn_vnet_byword_step_max_symbols, mvn_vnet_byword_step_states_list_f32, mvn_vnet_byword_step_list_max_symbols) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
+#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32, the list steps, mvn_vnet_byword_step_states_f32, mvn_vnet_byword_step_max_symbols, mvn_vnet_byword_step_states_list_f32, mvn_vnet_byword_step_list_max_symbols, mvn_va_byword_step_states_f32, mvn_va_byword_step_states_path_f32, mvn_va_byword_step_states_list_f32, mvn_va_byword_step_max_symbols, mvn_va_byword_step_list_max_symbols) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
 
 /* ABI version of the loaded library (== MVN_ABI_VERSION). */
 int mvn_version(void);
@@ -546,6 +546,50 @@ int mvn_vnet_byword_step_states_list_f32(const float *rx, int64_t rx_ld, const f
                                          float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                          int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
                                          int64_t delta_ld, int32_t *choice, mvn_stream_t stream);
+
+/*
+ * The three block steps of the CLASSICAL Viterbi detector -- mvn_va_byword_step_f32, mvn_va_byword_step_path_f32 and
+ * mvn_va_byword_step_list_f32 -- at S = 4, 8, 32, 64 or 128 states (S = 16 forwards to them, with their codes): same arguments, same
+ * outputs, one launch, a workgroup per word.  Word r uses row r % Bp of state_priors [Bp, S].  The definitions are those of the
+ * ViterbiNet steps at these state counts (mvn_vnet_byword_step_states_f32, _path_f32, _list_f32 above) with the branch cost
+ *   cost[t][s] = (y[t] - prior[s])^2 * 0.5 - fp32(log(sqrt(2 pi)))          (va_detector.py:64-68, every operation rounded on its own)
+ * in place of -logit[t][s]: the workgroup fills the on-chip image with them, one wavefront runs the recurrence with torch.min's and
+ * torch.argmin's rules (always: no fast path, no guard launch) and carries on with the walk, the list decode and the codec; labels are
+ * calculate_states with memory length log2 S.  Bit-identical on a data step:
+ *   running  dec to mvn_va_decode_f32;
+ *   path     dec to mvn_va_decode_surv_f32 -> mvn_traceback_f32;
+ *   list     dec to the path step's, delta, choice and msg to the definition of mvn_vnet_byword_step_states_list_f32 on this cost;
+ *   all      msg, nerr, enc, label_word and labels to mvn_rs_decode_bits_f32 / mvn_rs_encode_bits_f32 and the label rule on them.
+ * No weights share the LDS with the image, so the words may be longer than ViterbiNet's:
+ *   T <= mvn_va_byword_step_max_symbols(S) (running, path) = min(1024, what a CU's 160 KB hold next to the codec's state, in whole
+ *        bytes): 1024 at 4, 8, 16 and 32 states, 624 at 64, 312 at 128; 0 for a state count the steps do not serve;
+ *   T <= mvn_va_byword_step_list_max_symbols(S) (list) = min(512, the same for 4 S + 2 S + 4 bytes per symbol, 8 above 32 states):
+ *        512 at 4, 8, 16 and 32 states, 384 at 64, 192 at 128; 0 likewise.
+ * The check, in the order of the steps above: S not in {4, 8, 16, 32, 64, 128} -> MVN_E_STATES; R < 0, T not a multiple of 8,
+ * T / 8 <= nsym, nsym outside 1 .. 8 or T above the step's longest word -> MVN_E_DIMS; (list) list_bytes outside nsym .. T / 8,
+ * C(list_bytes, nsym) > 63 or delta_ld < T with delta given -> MVN_E_DIMS; a leading dimension too small -> MVN_E_DIMS; Bp < 1 ->
+ * MVN_E_PRIORS; R = 0 -> MVN_OK before any pointer is looked at; a required pointer NULL -> MVN_E_NULL (rx and state_priors may be
+ * NULL on a pilot step; tx on the list's data step when nerr, label_word and labels are NULL).  A pilot step detects nothing: through
+ * each of the three it is the running step's pilot (after the list's own limits were checked).
+ * mvn_va_byword_step_f32, _path_f32 and _list_f32 themselves keep answering MVN_E_STATES for S != 16.
+ * Non-finite costs: running and path dec keep torch.min's / torch.argmin's rules; the list's delta and choice are unspecified, the launch
+ * stays memory-safe and deterministic.  (Added without a bump of MVN_ABI_VERSION, like the other steps.)
+ */
+int32_t mvn_va_byword_step_max_symbols(int32_t S);
+int32_t mvn_va_byword_step_list_max_symbols(int32_t S);
+int mvn_va_byword_step_states_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                  float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                  float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                  int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+int mvn_va_byword_step_states_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors,
+                                       int64_t Bp, float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                       float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                       int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+int mvn_va_byword_step_states_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors,
+                                       int64_t Bp, float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                       float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                       int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                       int64_t delta_ld, int32_t *choice, mvn_stream_t stream);
 
 /* The MVN_* environment switches (A/B variants of the kernels) are read once per process; a caller that
  * changes them afterwards (the test-suite does) calls this to have them read again. */

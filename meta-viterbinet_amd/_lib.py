@@ -75,6 +75,11 @@ SIGNATURES = {
     "mvn_vnet_byword_step_list_max_symbols": (_i32, [_i32]),
     "mvn_vnet_byword_step_states_list_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
     "mvn_va_byword_step_list_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
+    "mvn_va_byword_step_max_symbols": (_i32, [_i32]),
+    "mvn_va_byword_step_list_max_symbols": (_i32, [_i32]),
+    "mvn_va_byword_step_states_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_va_byword_step_states_path_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_va_byword_step_states_list_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
     "mvn_reload_switches": (None, []),
     "mvn_isi_awgn_transmit": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, ctypes.c_double, _vp, _i64, _i64,
                                              _i32, _i32, _vp]),
@@ -169,7 +174,7 @@ def current_stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-STEP_STATES = (4, 8, 32, 64, 128)  # the state counts of mvn_vnet_byword_step_states[_path]_f32, next to the 16 of the six steps
+STEP_STATES = (4, 8, 32, 64, 128)  # the state counts of mvn_{vnet,va}_byword_step_states[_path|_list]_f32, next to the 16 of the six steps
 
 
 def step_max_symbols(n_states: int) -> int:
@@ -183,6 +188,18 @@ def list_max_symbols(n_states: int) -> int:
     return int(load().mvn_vnet_byword_step_list_max_symbols(n_states))
 
 
+def va_step_max_symbols(n_states: int) -> int:
+    """The longest word the classical detector's running and path steps serve at n_states (mvn_va_byword_step_max_symbols; 1024 at 16
+    states, 0: not served)."""
+    return int(load().mvn_va_byword_step_max_symbols(n_states))
+
+
+def va_list_max_symbols(n_states: int) -> int:
+    """The longest word the classical detector's list step serves at n_states (mvn_va_byword_step_list_max_symbols; 512 at 16 states,
+    0: not served)."""
+    return int(load().mvn_va_byword_step_list_max_symbols(n_states))
+
+
 class BywordStep:
     """One of the by-word block steps of include/mvn.h, mvn_{kind}_byword_step[_path|_list]_f32 (kind 'vnet' / 'va', decision
     'running' / 'path' / 'list'), for words of T symbols with nsym parity bytes (list: list_bytes least reliable bytes): the symbol
@@ -190,11 +207,14 @@ class BywordStep:
     n_states other than 16: mvn_vnet_byword_step_states_f32, the ViterbiNet running step, and with states_path=True (what
     harness._block_step and trials._cohort_steps pass) mvn_vnet_byword_step_states_path_f32 for decision 'path'; with
     states_list=True (what they pass as well) mvn_vnet_byword_step_states_list_f32 for kind 'vnet', decision 'list' at the state
-    counts of STEP_STATES; ValueError else."""
+    counts of STEP_STATES; with states_va=True (what harness._block_step and ecc.list_decode pass) kind 'va' at those state counts
+    resolves to mvn_va_byword_step_states[_path|_list]_f32; ValueError else."""
     def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None, n_states: int = 16, states_path: bool = False,
-                 states_list: bool = False):
+                 states_list: bool = False, states_va: bool = False):
         self.name = "mvn_%s_byword_step%s_f32" % (kind, {"running": "", "path": "_path", "list": "_list"}[decision])
-        if states_list and kind == "vnet" and decision == "list" and n_states in STEP_STATES:
+        if states_va and kind == "va" and n_states in STEP_STATES:
+            self.name = "mvn_va_byword_step_states%s_f32" % {"running": "", "path": "_path", "list": "_list"}[decision]
+        elif states_list and kind == "vnet" and decision == "list" and n_states in STEP_STATES:
             self.name = "mvn_vnet_byword_step_states_list_f32"
         elif n_states != 16:
             if kind != "vnet" or decision not in (("running", "path") if states_path else ("running",)):

@@ -19,6 +19,7 @@
 //   rs_codec.inc                           Reed-Solomon encode/decode
 //   byword_step.inc, byword_step_states.inc  one block step of the by-word evaluation in one launch (16 states; 4 ... 128 states)
 //   byword_list_states.inc                 that step with the list decode at 4 ... 128 states
+//   byword_step_states_va.inc              the three steps for the classical Viterbi detector at 4 ... 128 states
 //   online_train.inc, maml_train.inc       one-launch online training and MAML meta-learning steps
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -473,6 +474,7 @@ int ensure_dynamic_lds(const void *fn, size_t bytes);  // raises a kernel's dyna
 #include "byword_step.inc"
 #include "byword_step_states.inc"
 #include "byword_list_states.inc"
+#include "byword_step_states_va.inc"
 #include "online_train.inc"
 #include "maml_train.inc"
 #include "train_groups.inc"
@@ -1243,7 +1245,7 @@ int list_step_candidates(int32_t T, int32_t nsym, int32_t m) {
     return c <= kListMaxCand ? (int)c : 0;
 }
 
-// The state counts of byword_step_states.inc and byword_list_states.inc, in ONE place: fn(SC tag) picks the instantiation for S, as
+// The state counts of byword_step_states.inc, byword_list_states.inc and byword_step_states_va.inc, in ONE place: fn(SC tag) picks the instantiation for S, as
 // dispatch_states does for the training kernels; `other` is the answer for every other count (16 states among them).
 template <class Fn>
 int dispatch_step_states(int S, int other, Fn fn) {
@@ -1271,17 +1273,33 @@ int states_list_step_max_symbols(int32_t S) {
     return dispatch_step_states(S, 0, [](auto sc) { return states_list_max_symbols<decltype(sc)::value>(); });
 }
 
+// the same two limits of the classical detector's steps (byword_step_states_va.inc: no W3 image next to the word, so longer words at
+// 64 and 128 states)
+int va_states_step_max_symbols(int32_t S) {
+    if (S == 16) return kCoopMaxT;
+    return dispatch_step_states(S, 0, [](auto sc) { return states_va_max_symbols<decltype(sc)::value>(); });
+}
+
+int va_states_list_step_max_symbols(int32_t S) {
+    if (S == 16) return kListMaxT;
+    return dispatch_step_states(S, 0, [](auto sc) { return states_va_list_max_symbols<decltype(sc)::value>(); });
+}
+
 // The checks of a step, in the order the codes are documented in: the state count; the shapes; the list's limits; every leading
 // dimension; the rows of priors (VA); nothing to do (R = 0: MVN_OK before any pointer is looked at); the pointers.  A pilot detects
 // nothing, so a pilot of any decision is the running step and is checked as one: it needs tx and neither rx nor the priors (the
 // ViterbiNet weights are required all the same); only a list data step can do without tx, as long as nothing is compared with it.
 // Leaves the list's number of candidates in c.list.ncand.  any_states: the ViterbiNet running and path steps of
 // byword_step_states.inc, whose state counts and longest word are states_step_max_symbols', and the list step of
-// byword_list_states.inc, whose longest word is states_list_step_max_symbols' (a pilot's too: the list's limits come first).
+// byword_list_states.inc, whose longest word is states_list_step_max_symbols' (a pilot's too: the list's limits come first); for the
+// classical detector the steps of byword_step_states_va.inc and va_states_step_max_symbols' / va_states_list_step_max_symbols'.
 int step_check(StepCall &c, StepDecision decision, StepDetector detector, bool any_states = false) {
     const StepOut &o = c.out;
     const int T = c.T, nsym = c.nsym;
-    const int max_T = !any_states ? kCoopMaxT : decision == kStepList ? states_list_step_max_symbols(c.S) : states_step_max_symbols(c.S);
+    const bool va = detector == kStepVa;
+    const int max_T = !any_states ? kCoopMaxT
+                      : decision == kStepList ? (va ? va_states_list_step_max_symbols(c.S) : states_list_step_max_symbols(c.S))
+                                              : (va ? va_states_step_max_symbols(c.S) : states_step_max_symbols(c.S));
     if (any_states ? max_T == 0 : c.S != 16) return MVN_E_STATES;  // (the six steps of byword_step.inc exist for the 16-state detectors)
     if (c.R < 0 || T < 8 || (T & 7) || T > max_T || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
     if (decision == kStepList) {
@@ -1382,6 +1400,35 @@ int states_step_run(StepCall c, StepDecision decision) {
     const auto head = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.W[0], c.W[1], c.W[2], c.W[3], c.W[4], c.W[5], ws, c.dec, c.dec_ld,
                                       o.msg, o.msg_ld, o.enc, o.enc_ld, o.label_word, o.lw_ld, o.labels, o.lab_ld, o.nerr);
     return dispatch_step_states(c.S, MVN_E_STATES, [&](auto sc) { return states_step_launch<decltype(sc)::value>(c, decision, head); });
+}
+
+// mvn_va_byword_step_states_f32 / mvn_va_byword_step_states_path_f32 / mvn_va_byword_step_states_list_f32 at S != 16: one launch of
+// byword_step_states_va_kernel<S, NS>, byword_path_step_states_va_kernel<S, NS> or byword_list_step_states_va_kernel<S, NS>, the same
+// workgroups and the same dynamic LDS per symbol as the ViterbiNet steps above, up to the classical detector's own longest word
+template <int S, class Head>
+int va_states_step_launch(const StepCall &c, StepDecision decision, const Head &head) {
+    if (decision == kStepList) {
+        const ListOut &l = c.list;
+        return step_launch(byword_list_step_states_va_kernel<S, 2>, byword_list_step_states_va_kernel<S, 8>, c, 64 * kStatesWaves,
+                           (size_t)c.T * states_list_symbol_bytes<S>(), (size_t)states_va_list_max_symbols<S>() * states_list_symbol_bytes<S>(),
+                           std::tuple_cat(head, std::make_tuple(l.delta, l.delta_ld, l.choice, c.T, c.nsym, l.m, l.ncand)));
+    }
+    const size_t dyn = c.pilot ? 0 : (size_t)c.T * S * sizeof(float), dyn_max = (size_t)states_va_max_symbols<S>() * S * sizeof(float);
+    if (decision == kStepPath)
+        return step_launch(byword_path_step_states_va_kernel<S, 2>, byword_path_step_states_va_kernel<S, 8>, c, 64 * kStatesWaves, dyn,
+                           dyn_max, std::tuple_cat(head, std::make_tuple(c.T, c.nsym)));
+    return step_launch(byword_step_states_va_kernel<S, 2>, byword_step_states_va_kernel<S, 8>, c, 64 * kStatesWaves, dyn, dyn_max,
+                       std::tuple_cat(head, std::make_tuple(c.T, c.nsym, c.pilot)));
+}
+
+int va_states_step_run(StepCall c, StepDecision decision) {
+    const int e = step_check(c, decision, kStepVa, true);
+    if (e != MVN_OK || c.R == 0) return e;
+    if (c.pilot) decision = kStepRunning;  // (the path and list kernels are data steps)
+    const StepOut &o = c.out;
+    const auto head = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.priors, c.Bp, c.dec, c.dec_ld, o.msg, o.msg_ld, o.enc, o.enc_ld,
+                                      o.label_word, o.lw_ld, o.labels, o.lab_ld, o.nerr);
+    return dispatch_step_states(c.S, MVN_E_STATES, [&](auto sc) { return va_states_step_launch<decltype(sc)::value>(c, decision, head); });
 }
 
 }  // namespace
@@ -1888,6 +1935,47 @@ int mvn_va_byword_step_list_f32(const float *rx, int64_t rx_ld, const float *tx,
     return step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {delta, delta_ld, choice, list_bytes, 0},
                      {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
                     kStepList, kStepVa);
+}
+
+int32_t mvn_va_byword_step_max_symbols(int32_t S) { return va_states_step_max_symbols(S); }
+
+int mvn_va_byword_step_states_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                  float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                  float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                  int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    if (S == 16)  // one call for every state count: the 16-state step, with its own checks
+        return mvn_va_byword_step_f32(rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word, lw_ld,
+                                      labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    return va_states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                               {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                              kStepRunning);
+}
+
+int mvn_va_byword_step_states_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors,
+                                       int64_t Bp, float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                       float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                       int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    if (S == 16)
+        return mvn_va_byword_step_path_f32(rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word,
+                                           lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, stream);
+    return va_states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                               {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                              kStepPath);
+}
+
+int32_t mvn_va_byword_step_list_max_symbols(int32_t S) { return va_states_list_step_max_symbols(S); }
+
+int mvn_va_byword_step_states_list_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors,
+                                       int64_t Bp, float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                       float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                       int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
+                                       int64_t delta_ld, int32_t *choice, mvn_stream_t stream) {
+    if (S == 16)
+        return mvn_va_byword_step_list_f32(rx, rx_ld, tx, tx_ld, state_priors, Bp, dec, dec_ld, msg, msg_ld, enc, enc_ld, label_word,
+                                           lw_ld, labels, lab_ld, nerr, R, T, nsym, pilot, S, list_bytes, delta, delta_ld, choice, stream);
+    return va_states_step_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr},
+                               {delta, delta_ld, choice, list_bytes, 0}, {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                              kStepList);
 }
 
 void mvn_reload_switches(void) { load_switches(); }

@@ -87,7 +87,8 @@ def list_decode(detector, rx: torch.Tensor, n_symbols: int, list_bytes=None, ret
     combination and filled, and of those codewords and the hard-decoded one the one whose own path through the detector's branch
     costs is cheapest wins (include/mvn.h has the exact arithmetic).
     detector: a 16-state VNETDetector or VADetector (gamma / count: what VADetector.forward takes to find the words' channel), or a
-    VNETDetector at 4, 8, 32, 64 or 128 states (mvn_vnet_byword_step_states_list_f32, T <= _lib.list_max_symbols(n_states));
+    VNETDetector at 4, 8, 32, 64 or 128 states (mvn_vnet_byword_step_states_list_f32, T <= _lib.list_max_symbols(n_states)), or a
+    VADetector at those state counts (mvn_va_byword_step_states_list_f32, T <= _lib.va_list_max_symbols(n_states));
     rx [B, T], T a multiple of 8 and <= 512.  Returns (msg [B, T - 8 n_symbols] fp32 bits, choice [B] int32: 0 = the hard decoder's
     word, c > 0 = the c-th erasure pattern) and, with return_delta, delta [B, T]."""
     from .detectors import VADetector, VNETDetector
@@ -96,12 +97,14 @@ def list_decode(detector, rx: torch.Tensor, n_symbols: int, list_bytes=None, ret
         raise ValueError(f"list_decode needs a Viterbi / ViterbiNet detector, not {type(detector).__name__}")
     T = rx.shape[-1]
     S = getattr(detector, "n_states", None)
-    states = isinstance(detector, VNETDetector) and S in _lib.STEP_STATES  # mvn_vnet_byword_step_states_list_f32
+    states = S in _lib.STEP_STATES  # mvn_vnet_byword_step_states_list_f32 / mvn_va_byword_step_states_list_f32
     if S != 16 and not states:
-        raise ValueError("list_decode runs the 16-state kernels, and the ViterbiNet kernels at 4, 8, 32, 64 and 128 states")
+        raise ValueError("list_decode runs the 16-state kernels, and the ViterbiNet and Viterbi kernels at 4, 8, 32, 64 and 128 states")
     m = list_step_bytes(T, n_symbols, list_bytes, "list_decode")
-    if states and T > _lib.list_max_symbols(S):
-        raise ValueError(f"list_decode serves words of up to {_lib.list_max_symbols(S)} symbols at {S} states, got T = {T}")
+    if states:
+        longest = _lib.va_list_max_symbols(S) if isinstance(detector, VADetector) else _lib.list_max_symbols(S)
+        if T > longest:
+            raise ValueError(f"list_decode serves words of up to {longest} symbols at {S} states, got T = {T}")
     if isinstance(detector, VADetector) and gamma is None:
         raise ValueError("list_decode with a VADetector needs gamma (what VADetector.forward takes to find the words' channel)")
     y = _bits(rx)
@@ -121,7 +124,7 @@ def list_decode(detector, rx: torch.Tensor, n_symbols: int, list_bytes=None, ret
         if detector.transmission_lengths["val"] != T:
             raise ValueError(f"the detector's 'val' length {detector.transmission_lengths['val']} is not the word length {T}")
         kind, front = "vnet", (*[_lib.ptr(_lib.f32c(p)) for p in detector._params()], None)
-    _lib.BywordStep(kind, "list", T, n_symbols, m, n_states=S, states_list=True)(dev, _lib.ptr(y), y.stride(0), None, K, front, {"msg": (_lib.ptr(msg), K)}, None, B,
+    _lib.BywordStep(kind, "list", T, n_symbols, m, n_states=S, states_list=True, states_va=True)(dev, _lib.ptr(y), y.stride(0), None, K, front, {"msg": (_lib.ptr(msg), K)}, None, B,
                                                    False, delta=_lib.ptr(delta), choice=_lib.ptr(choice))
     return (msg, choice, delta) if return_delta else (msg, choice)
 

@@ -345,7 +345,9 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     word and the buffered label word follow from it.  It exists in the one-launch step only: ValueError when the step's conditions
     (_fused_step_applies, fused_step=True) or T <= 512 do not hold.  A ViterbiNet detector at 4, 8, 32, 64 or 128 states takes
     mvn_vnet_byword_step_states_list_f32 (_states_list_step_applies: the path step's conditions and words up to
-    _lib.list_max_symbols(n_states) symbols); 2 and 256 states and a VADetector off 16 states have no list step."""
+    _lib.list_max_symbols(n_states) symbols).  A VADetector at 4, 8, 32, 64 or 128 states takes mvn_va_byword_step_states_f32, _path_f32
+    and _list_f32 under the 16-state VA rule (_va_states_step_applies: words up to _lib.va_step_max_symbols(n_states), for 'list'
+    _lib.va_list_max_symbols(n_states), symbols); 2 and 256 states have no list step."""
     import copy
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
@@ -371,10 +373,14 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     N = tx.shape[0]
     ser_by_word = np.zeros(N)
     K = tx.shape[1]
-    fused = fused_step and (_fused_step_applies(detector, rx, n_symbols, pass_count, decision)
-                            or (decision == "list" and _states_list_step_applies(detector, rx, n_symbols, pass_count)))
+    va_states = fused_step and _va_states_step_applies(detector, rx, n_symbols, pass_count, decision)  # a VADetector off 16 states
+    fused = va_states or (fused_step and (_fused_step_applies(detector, rx, n_symbols, pass_count, decision)
+                                          or (decision == "list" and _states_list_step_applies(detector, rx, n_symbols, pass_count))))
     if decision == "list":
-        list_bytes = _list_step_bytes(detector, rx, n_symbols, pass_count, fused_step, list_bytes)
+        if not va_states:
+            _va_states_list_conditions(detector, rx, n_symbols, pass_count, fused_step)
+        list_bytes = (list_step_bytes(rx.shape[1], n_symbols, list_bytes) if va_states else
+                      _list_step_bytes(detector, rx, n_symbols, pass_count, fused_step, list_bytes))
     elif list_bytes is not None:
         raise ValueError("list_bytes belongs to decision='list'")
     step = _block_step(detector, rx.shape[1], n_symbols, decision, list_bytes) if fused else None
@@ -607,6 +613,48 @@ def _states_list_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_c
             and rx.shape[1] <= _lib.list_max_symbols(S))
 
 
+def _va_states_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, decision: str = "running") -> bool:
+    """A VADetector at 4, 8, 32, 64 or 128 states takes one launch per block step (mvn_va_byword_step_states_f32, _path_f32, _list_f32)
+    under the 16-state VA rule of _fused_step_applies: the detector's length is the word length, ONE row of state priors (the word's
+    own with pass_count, or the table's only row), words of whole bytes longer than the parity, nsym 1 ... 8, and T within the rule's
+    longest word (_lib.va_step_max_symbols / _lib.va_list_max_symbols).  Consulted BEFORE _fused_step_applies,
+    _states_list_step_applies and _list_step_bytes, which keep answering for such a detector what they answered before this step
+    existed.  eval_by_word takes the step by default at every one of these state counts: it measured faster than the separate launches
+    at each, for 'running' and for 'path' (profiles/va_states_step_time.txt); 'list' has no other route."""
+    from . import _lib
+    from .detectors import VADetector
+
+    T = rx.shape[1]
+    S = getattr(detector, "n_states", None)
+    if not (isinstance(detector, VADetector) and S in _lib.STEP_STATES and decision in ("running", "path", "list")):
+        return False
+    if not (rx.is_cuda and T % 8 == 0 and T >= 8 and 1 <= n_symbols <= 8 and T // 8 > n_symbols):
+        return False
+    if not (detector.transmission_length == T and (pass_count or detector.val_words == 1)):
+        return False
+    return T <= (_lib.va_list_max_symbols(S) if decision == "list" else _lib.va_step_max_symbols(S))
+
+
+def _va_states_list_conditions(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, fused_step: bool) -> None:
+    """decision='list' with a VADetector at 4, 8, 32, 64 or 128 states that _va_states_step_applies turned down: the ValueError that
+    names the condition (there is no other route to fall back to).  Every other detector: nothing (_list_step_bytes speaks for it)."""
+    from . import _lib
+    from .detectors import VADetector
+
+    S = getattr(detector, "n_states", None)
+    if not (isinstance(detector, VADetector) and S in _lib.STEP_STATES and rx.is_cuda and fused_step):
+        return
+    T = rx.shape[1]
+    list_step_bytes(T, n_symbols, None)
+    if T > _lib.va_list_max_symbols(S):
+        raise ValueError(f"decision='list' serves words of up to {_lib.va_list_max_symbols(S)} symbols at {S} states with a VADetector "
+                         f"(branch costs, forward metrics and survivors stay in LDS), got T = {T}")
+    if detector.transmission_length != T:
+        raise ValueError(f"decision='list': the detector's transmission_length {detector.transmission_length} is not the word length {T}")
+    if not (pass_count or detector.val_words == 1):
+        raise ValueError("decision='list': a VADetector with several rows of state priors needs pass_count=True")
+
+
 def _list_step_bytes(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, fused_step: bool, list_bytes) -> int:
     """decision='list' exists in the one-launch block step only: the validated list_bytes, or a ValueError that names the
     condition that does not hold (there is no other route to fall back to)."""
@@ -648,7 +696,7 @@ def _block_step(detector, T: int, n_symbols: int, decision: str, list_bytes):
     from .detectors import VADetector
 
     return _lib.BywordStep("va" if isinstance(detector, VADetector) else "vnet", decision, T, n_symbols, list_bytes,
-                           n_states=detector.n_states, states_path=True, states_list=True)
+                           n_states=detector.n_states, states_path=True, states_list=True, states_va=True)
 
 
 def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, pilot: bool, nerr: torch.Tensor,
@@ -668,8 +716,8 @@ def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: 
     T, K = rxw.shape[1], txw.shape[1]
     dev = rxw.device
     if isinstance(detector, VADetector):
-        pri = detector._priors_table(rxw, gamma, "val", count)  # [W, 16] (one row when count is given)
-        assert pri.shape[0] == 1  # (_fused_step_applies sends every other table to the separate launches)
+        pri = detector._priors_table(rxw, gamma, "val", count)  # [W, n_states] (one row when count is given)
+        assert pri.shape[0] == 1  # (_fused_step_applies / _va_states_step_applies send every other table to the separate launches)
         front = (_lib.ptr(pri), 1)
     else:
         front = (*[_lib.ptr(_lib.f32c(p)) for p in detector._params()], None)
