@@ -255,6 +255,30 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
                                  mvn_stream_t stream);
 
 /*
+ * Joint training of the ViterbiNet MLP in ONE launch: the inner loop of Trainer.train() (trainers/trainer.py:470-479), one
+ * optimizer step per word -- mvn_vnet_online_train_f32 with a word axis, the counterpart of mvn_lstm_train_f32's.
+ *   y [n_words, K or more] fp32 received words (row stride y_ld), labels int32 [n_words, K or more] trellis states (row stride
+ *   labels_ld); K: the positions of a word that carry a label (with use_ecc the reference hands calc_loss the 120 message bits
+ *   against a 136-symbol received word: K = 120, y_ld = 136); iteration i trains on word word_of_iter[i] (device int32 [n_iter]).
+ *   batch_idx [n_iter, M] device int32 positions in [0, K) (select_batch draws from arange(K), trainer.py:534-544; a position
+ *   drawn twice counts twice), or NULL / M == 0: all K positions in every iteration.
+ *   W1..b3, adam_m / adam_v [P], step0, lr, beta1 (Adam, or the MVN_BETA1_RMSPROP / MVN_BETA1_SGD tags), beta2, eps, loss_out
+ *   [n_iter] or NULL, S <= 128: as mvn_vnet_online_train_f32.
+ * One 1024-thread workgroup (online_train_words_kernel<S or 0>: the same chunk code, sums and optimizer update as
+ * online_train_kernel<S, false>); with word_of_iter[i] naming rows that hold the same word the results are bit for bit those
+ * of mvn_vnet_online_train_f32 on that word.  No workspace: a whole-word iteration also runs on the one workgroup.
+ * Returns, in this order, before anything is launched: MVN_E_DIMS (n_iter < 0, n_words < 1, K < 1, K above a row stride, a row
+ * stride above INT32_MAX, M < 0, M > K, step0 < 0), MVN_E_STATES (S above 128 or not a power of two), MVN_OK for n_iter == 0
+ * (nothing is read or written), MVN_E_NULL (y, labels, word_of_iter, a weight or a moment pointer is NULL), else the launch's
+ * result.  The caller's duty: every entry of word_of_iter lies in [0, n_words) and every entry of batch_idx in [0, K) -- they are
+ * not checked (the call cannot see device memory) and an entry outside is read out of bounds.
+ */
+int mvn_vnet_train_words_f32(const float *y, int64_t y_ld, const int32_t *labels, int64_t labels_ld, int64_t n_words, int32_t K,
+                             const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1, float *b1,
+                             float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0, float lr,
+                             float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream);
+
+/*
  * n_steps online meta-learning steps of Meta-ViterbiNet in ONE launch: Trainer.meta_train_loop
  * (python_code/trainers/trainer.py:425-453) with METAVNETTrainer.calc_loss (metavnet_trainer.py:41-50):
  *   inner SGD step on the support words (lr = meta_lr), query loss through the updated weights, meta-gradient w.r.t.
@@ -303,7 +327,7 @@ typedef struct mvn_train_trial {
     const float *y;           /* online: the word [T]; maml: the buffered received words [Nw, T] */
     const int32_t *labels;    /* online: [T]; maml: [Nw, T] (calculate_states of the buffered label words) */
     const int32_t *idx;       /* online: batch_idx [n, M] or NULL = whole word; maml: support_idx [n, W] */
-    const int32_t *query_idx; /* maml: [n]; online: unused */
+    const int32_t *query_idx; /* maml: [n]; online: unused (mvn_vnet_train_words_f32 carries word_of_iter here) */
     const float *w_in[6];     /* W1, b1, W2, b2, W3, b3 read when the trial starts (e.g. the saved detector, trainer.py:275) */
     float *w_out[6];          /* ... written when it ends (may alias w_in) */
     float *w_out2[6];         /* optional second copy of the result (all six NULL: none) */

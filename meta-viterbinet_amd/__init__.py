@@ -6,8 +6,8 @@ from .detectors import HIDDEN1_SIZE, HIDDEN2_SIZE, META_VNETDetector, VADetector
 from .ecc import list_decode, rs_decode, rs_encode
 from .lstm import LSTMDetector, LSTMMetaTrainer, LSTMOnlineTrainer, MetaLSTMDetector
 from .lstm_trials import LSTMTrialBank, lstm_decode_trials
-from .harness import (data_indices, detect_by_word, eval_by_word, eval_counters, replica_eval, shard_range, sharded_eval,
-                      single_eval_at_point, synthetic_words, va_monte_carlo, vnet_monte_carlo)
+from .harness import (data_indices, detect_by_word, eval_by_word, eval_counters, joint_train, meta_train, reference_word_source,
+                      replica_eval, shard_range, sharded_eval, single_eval_at_point, synthetic_words, va_monte_carlo, vnet_monte_carlo)
 from .meta import GraphedMetaStep, copy_model, meta_train_loop
 from .online import OnlineTrainer
 from .trials import TrialBank, TrialDraws, eval_by_word_batched
@@ -21,5 +21,5 @@ __all__ = [
     "estimate_channel", "BPSKModulator", "transmit", "generate_words", "ReferenceWordStream", "rs_encode", "rs_decode", "list_decode", "OnlineTrainer", "meta_train_loop", "GraphedMetaStep", "copy_model",
     "shard_range", "data_indices", "synthetic_words", "va_monte_carlo", "vnet_monte_carlo", "eval_counters", "single_eval_at_point",
     "sharded_eval", "detect_by_word", "eval_by_word", "replica_eval", "TrialBank", "TrialDraws", "eval_by_word_batched",
-    "LSTMTrialBank", "lstm_decode_trials",
+    "LSTMTrialBank", "lstm_decode_trials", "joint_train", "meta_train", "reference_word_source",
 ]

@@ -1148,9 +1148,15 @@ int train_run_chunked(void (*k_many)(P...), void (*k_one)(P...), const TrainCall
 }
 
 // The online (maml false: M_or_W = M, meta_lr and second_order unused) and the meta-learning trainer, one trial by value or R trials
+// `words` (online, one trial, no workspace: mvn_vnet_train_words_f32): the word axis -- y / labels are rows ld_y / ld_lab apart, T counts
+// a word's labelled positions and the trial's query_idx holds word_of_iter.  Without a workspace plan_train never spreads a call over
+// workgroups, so the plan is the single workgroup's, with the state constant of online_train_kernel<SC, false>.
+struct TrainWords {
+    int ld_y, ld_lab;
+};
 int launch_train(bool maml, const mvn_train_trial_t &one, const mvn_train_trial_t *many, int R, int T, int M_or_W, float meta_lr,
                  int second_order, float lr, float beta1, float beta2, float eps, int S, void *workspace, size_t workspace_bytes,
-                 hipStream_t st) {
+                 hipStream_t st, const TrainWords *words = nullptr) {
     const TrainCall c = {plan_train(maml ? (second_order ? 2 : 1) : 0, many != nullptr, R, T, M_or_W, S, workspace != nullptr, workspace_bytes),
                          one, many, R, S, workspace, st};
     if (c.plan.groups && (reinterpret_cast<uintptr_t>(workspace) & 15)) return MVN_E_WORKSPACE;
@@ -1161,6 +1167,11 @@ int launch_train(bool maml, const mvn_train_trial_t &one, const mvn_train_trial_
         constexpr int SC1M = SC1 == 32 ? 0 : SC1;   // (the run-time form for R trials at 32 states)
         constexpr int SC = SC1 > 32 ? 0 : SC1;      // the chunked kernels and R meta-learning trials: up to 32 states (plan_train, the entry point)
         constexpr int SCM = SC == 32 ? 0 : SC;
+        if (words) {
+            if (maml || many || c.plan.form != kTrainPerTrial) return MVN_E_DIMS;  // (no entry point asks for these)
+            return train_run(online_train_words_kernel<SC1>, online_train_words_kernel<SC1>, c, kTrainThreads,
+                             std::tuple_cat(std::make_tuple(T, M_or_W, words->ld_y, words->ld_lab), adam));
+        }
         if (c.plan.form == kTrainChunked) {
             if (maml) return train_run_chunked(maml_train_groups_kernel<SCM, true>, maml_train_groups_kernel<SC, false>, c, meta);
             return train_run_chunked(online_train_groups_kernel<SCM, true>, online_train_groups_kernel<SC, false>, c,
@@ -1741,6 +1752,23 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
                                             beta1, beta2, step0, n_iter);
     return launch_train(false, d, nullptr, 1, T, batch_idx ? M : 0, 0.0f, 0, lr, beta1, beta2, eps, S, workspace, workspace_bytes,
                         (hipStream_t)stream);
+}
+
+int mvn_vnet_train_words_f32(const float *y, int64_t y_ld, const int32_t *labels, int64_t labels_ld, int64_t n_words, int32_t K,
+                             const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1, float *b1,
+                             float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0, float lr,
+                             float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream) {
+    if (n_iter < 0 || n_words < 1 || K < 1 || y_ld < K || labels_ld < K || M < 0 || M > K || step0 < 0) return MVN_E_DIMS;
+    if (y_ld > INT32_MAX || labels_ld > INT32_MAX) return MVN_E_DIMS;  // (the kernel takes the row strides as 32-bit arguments)
+    if (!valid_states(S) || S > 128) return MVN_E_STATES;
+    if (n_iter == 0) return MVN_OK;
+    if (!y || !labels || !word_of_iter || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !adam_m || !adam_v) return MVN_E_NULL;
+    // batch_idx == NULL or M == 0: all K positions of the word in every iteration (batch_idx is not read)
+    const int32_t *idx = M > 0 ? batch_idx : nullptr;
+    const mvn_train_trial_t d = train_trial(y, labels, idx, word_of_iter, {W1, b1, W2, b2, W3, b3}, adam_m, adam_v, loss_out, nullptr,
+                                            beta1, beta2, step0, n_iter);
+    const TrainWords words = {(int)y_ld, (int)labels_ld};
+    return launch_train(false, d, nullptr, 1, K, idx ? M : 0, 0.0f, 0, lr, beta1, beta2, eps, S, nullptr, 0, (hipStream_t)stream, &words);
 }
 
 size_t mvn_vnet_train_lds_bytes(int32_t kind, int32_t S) {

@@ -6,7 +6,7 @@ Blocks (words) are independent, so the batch axis is split contiguously across r
 decodes its rows, counts errors on the device as integers, and ONE all_reduce(SUM) of an int64[4]
 tensor {bit_errors, bits, frame_errors, frames} (RCCL over xGMI when backend='nccl') ends the run.
 Decisions are never gathered.  Integer counters make 1/2/4/8-GPU results identical."""
-from typing import Callable, Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -730,3 +730,181 @@ def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: 
         out = {"dec": (_lib.ptr(got[0]), T), "enc": (_lib.ptr(got[1]), T)} if outputs else {}
     step(dev, _lib.ptr(rxw), T, _lib.ptr(txw), K, front, out, _lib.ptr(nerr), 1, pilot)
     return got
+
+
+# ---- the two offline loops that produce the weights every evaluation above starts from: Trainer.train() (trainer.py:455-490) and
+# Trainer.meta_train() (trainer.py:383-423), for one SNR each
+class JointTrainResult(NamedTuple):
+    losses: np.ndarray        # [n_minibatches] float64: the steps' losses of a minibatch summed like `current_loss +=` (trainer.py:479)
+    ser: np.ndarray           # [n_minibatches] float64: single_eval_at_point's ser after each minibatch
+    best_ser: float
+    best_weights: list        # six tensors (parameters() order): the copy kept by the strict `ser < best_ser` (trainer.py:485-487)
+    best_minibatch: int       # 0-based
+    step_losses: np.ndarray   # [n_minibatches, steps] float32
+    counters: np.ndarray      # [n_minibatches, 4] int64 {bit_errors, bits, frame_errors, frames} of each validation
+
+
+class MetaTrainResult(NamedTuple):
+    losses: np.ndarray        # [n_minibatches] float64: the query losses of a minibatch summed (trainer.py:416)
+    ser: np.ndarray           # [n_minibatches] float64
+    weights: list             # per minibatch the six tensors saved after it (save_weights runs every minibatch, trainer.py:423)
+    step_losses: list         # per minibatch float32 [steps]: one per j_hat value
+    counters: np.ndarray      # [n_minibatches, 4] int64
+    j_hat: list               # per minibatch the int64 j_hat values used
+
+
+def reference_word_source(memory_length: int, device, snr: float, gamma: float, block_length: int = 120, n_symbols: int = 0,
+                          train_frames: int = 12, val_frames: int = 12, subframes_in_frame: int = 25,
+                          channel_coefficients: str = "time_decay", noisy_est_var: float = 0, fading_in_channel: bool = False,
+                          fading_in_decoder: bool = False, fading_taps_type: int = 1, noise_seed: int = 3450002,
+                          word_seed: int = 7860002) -> Callable:
+    """words(minibatch, phase) for joint_train / meta_train: the two datasets of initialize_dataloaders (trainer.py:187-217) on ONE
+    channel.ReferenceWordStream -- the reference's datasets share their two RandomState streams, so 'train' and 'val' draws continue
+    one sequence in call order.  'train': frames * subframes words through time_decay taps, fading = fading_in_decoder; 'val': the
+    configured channel_coefficients, fading = fading_in_channel; word i of a draw uses estimate_channel(..., index=i)
+    (channel_dataset.py:55-85).  Returns (b [n, block_length] message bits, y [n, block_length + 8 n_symbols]), on the device."""
+    from .channel import ReferenceWordStream
+
+    stream = ReferenceWordStream(block_length, memory_length, device, n_symbols, noise_seed, word_seed)
+    n = {"train": train_frames * subframes_in_frame, "val": val_frames * subframes_in_frame}
+    coeff = {"train": "time_decay", "val": channel_coefficients}
+    fading = {"train": fading_in_decoder, "val": fading_in_channel}
+
+    def words(minibatch: int, phase: str):
+        h = np.concatenate([estimate_channel(memory_length, gamma, coeff[phase], noisy_est_var, fading[phase], i, fading_taps_type)
+                            for i in range(n[phase])], axis=0)
+        return stream.draw(n[phase], h, snr)
+
+    return words
+
+
+def _word_source(words, word_source, detector, online_trainer, snr, gamma, n_symbols, subframes_in_frame) -> Callable:
+    """The caller's words(minibatch, phase), or reference_word_source on the detector's device with the trainer's memory length;
+    word_source: further keyword arguments of reference_word_source (block_length, train_frames, val_frames, the channel's
+    settings, the two seeds)."""
+    if words is not None:
+        if word_source:
+            raise ValueError("word_source holds the settings of the default word source: give it or `words`, not both")
+        return words
+    return reference_word_source(online_trainer.memory_length, next(detector.parameters()).device, snr, gamma, n_symbols=n_symbols,
+                                 subframes_in_frame=subframes_in_frame, **(word_source or {}))
+
+
+def _params_copy(detector) -> list:
+    return [p.detach().clone() for p in detector.parameters()]
+
+
+def _validation(detector, tx, rx, snr, gamma, rows, n_symbols, evaluate):
+    """(ser, counters int64[4] on the host) of one validation draw: single_eval_at_point (trainer.py:222-241), or the caller's
+    evaluate(detector, tx, rx) -> (ser, counters)."""
+    if evaluate is not None:
+        ser, counters = evaluate(detector, tx, rx)
+    else:
+        ser, _, counters = single_eval_at_point(detector, tx, rx, snr, gamma, rows, n_symbols=n_symbols)
+    return float(ser), np.asarray(torch.as_tensor(counters).cpu(), dtype=np.int64).reshape(4)
+
+
+def joint_train(detector, online_trainer, snr: float, gamma: float, n_minibatches: int, words: Optional[Callable] = None,
+                n_symbols: int = 0, subframes_in_frame: int = 25, batch_idx=None, full_word: bool = False,
+                evaluate: Optional[Callable] = None, word_source: Optional[dict] = None, verbose: bool = False) -> JointTrainResult:
+    """The body of Trainer.train() for one SNR (trainer.py:468-489) on `detector` as it stands (the reference initialises detector and
+    optimizer just before, :466-467: pass a fresh VNETDetector and OnlineTrainer).  For each of n_minibatches:
+        tx, rx = words(minibatch, 'train')              the minibatch's training words: tx [n, K] message bits, rx [n, T]
+        online_trainer.train_words(tx, rx, ...)         one optimizer step per word, in ONE launch on the kernel route (:476-479)
+        tx, rx = words(minibatch, 'val') -> ser         single_eval_at_point over the data rows (:482; n_symbols > 0 = use_ecc)
+        ser < best_ser: keep a copy of the weights      (:485-487; strict, and the first minibatch always wins against inf)
+    words: a callable (minibatch number from 0, 'train' | 'val') -> (tx, rx), e.g. one that replays recorded words; None: the
+    reference's own source, reference_word_source(**word_source) (channel.ReferenceWordStream with the 'train' / 'val' settings of
+    initialize_dataloaders; it transmits on the device).  batch_idx: the select_batch draws -- None: online_trainer.select_batches(K, n) per minibatch; an array
+    [n_minibatches, n, M] of recorded draws; or a callable minibatch -> [n, M].  full_word=True: every step uses the whole word.
+    evaluate(detector, tx, rx) -> (ser, counters [4]): replaces single_eval_at_point (a CPU detector has no 'val' path here).
+    The data rows of a validation are those whose number is no multiple of subframes_in_frame (trainer.py:100-102)."""
+    words = _word_source(words, word_source, detector, online_trainer, snr, gamma, n_symbols, subframes_in_frame)
+    best_ser, best_weights, best_minibatch = float("inf"), None, -1
+    losses, sers, step_losses, counters = [], [], [], []
+    for mb in range(n_minibatches):
+        tx, rx = words(mb, "train")
+        idx = None
+        if not full_word and batch_idx is not None:
+            idx = torch.as_tensor(np.asarray(batch_idx(mb) if callable(batch_idx) else batch_idx[mb]))
+        loss = online_trainer.train_words(tx, rx, batch_idx=idx, full_word=full_word, return_loss=True)
+        vtx, vrx = words(mb, "val")
+        rows = torch.tensor([i for i in range(vtx.shape[0]) if i % subframes_in_frame != 0], dtype=torch.int64, device=vtx.device)
+        ser, cnt = _validation(detector, vtx, vrx, snr, gamma, rows, n_symbols, evaluate)
+        if hasattr(online_trainer, "check_status"):
+            online_trainer.check_status()
+        sl = loss.detach().cpu().numpy().astype(np.float32)
+        step_losses.append(sl)
+        current_loss = 0.0
+        for v in sl:  # `current_loss += loss.item()` (trainer.py:479)
+            current_loss += float(v)
+        losses.append(current_loss)
+        sers.append(ser)
+        counters.append(cnt)
+        if verbose:
+            print(f"Minibatch {mb + 1}, ser - {ser}, loss {current_loss}")
+        if ser < best_ser:
+            best_ser, best_weights, best_minibatch = ser, _params_copy(detector), mb
+    return JointTrainResult(np.asarray(losses), np.asarray(sers), best_ser, best_weights, best_minibatch,
+                            np.stack(step_losses) if step_losses else np.zeros((0, 0), np.float32),
+                            np.stack(counters) if counters else np.zeros((0, 4), np.int64))
+
+
+def meta_train(detector, meta_detector, online_trainer, snr: float, gamma: float, n_minibatches: int,
+               words: Optional[Callable] = None, n_symbols: int = 0, subframes_in_frame: int = 25, window_size: int = 1,
+               meta_j_num: int = 10, meta_lr: float = 0.1, MAML: bool = True, j_hat=None, evaluate: Optional[Callable] = None,
+               encode: Optional[Callable] = None, word_source: Optional[dict] = None, verbose: bool = False) -> MetaTrainResult:
+    """The body of Trainer.meta_train() for one SNR (trainer.py:398-423) on `detector` as it stands.  For each of n_minibatches:
+        tx, rx = words(minibatch, 'train')                                              (:400)
+        j_hat = unique(randint(window_size, n_words, [meta_j_num]))                     (:404-406; or the recorded values)
+        tx = rs_encode(tx, n_symbols) when n_symbols > 0                                (:407-410)
+        one step per j_hat: support words j_hat + arange(-window_size, 0), query j_hat  (:413-417)
+        tx, rx = words(minibatch, 'val') -> ser                                         (:420)
+        the weights are saved after every minibatch                                     (:423)
+    All steps of a minibatch are ONE online_trainer.maml_training call (one launch) with Adam on the kernel route; RMSprop, SGD, a CPU
+    detector and use_kernel=False run them through meta.meta_train_loop on the same optimizer state, as eval_by_word does.
+    j_hat: None, a sequence (per minibatch the values to use) or a callable minibatch -> values.  words, word_source, evaluate: as
+    joint_train.
+    encode(tx, n_symbols) -> codewords: replaces mvn.rs_encode (which runs on the device only)."""
+    from .meta import meta_train_loop
+
+    words = _word_source(words, word_source, detector, online_trainer, snr, gamma, n_symbols, subframes_in_frame)
+    if n_symbols > 0 and encode is None:
+        encode = rs_encode
+    kernel = (online_trainer.words_kernel_route() and online_trainer.optimizer_type == "Adam") if hasattr(online_trainer, "words_kernel_route") else False
+    losses, sers, weights, step_losses, counters, j_used = [], [], [], [], [], []
+    for mb in range(n_minibatches):
+        tx, rx = words(mb, "train")
+        dev = rx.device
+        if j_hat is None:
+            j = torch.unique(torch.randint(low=window_size, high=tx.shape[0], size=[meta_j_num]))
+        else:
+            j = torch.as_tensor(np.asarray(j_hat(mb) if callable(j_hat) else j_hat[mb])).long().reshape(-1)
+        j = j.to(dev)
+        if n_symbols > 0:
+            tx = torch.as_tensor(encode(tx, n_symbols)).to(device=dev, dtype=torch.float32)
+        sup = j.reshape(-1, 1) + torch.arange(-window_size, 0, device=dev).reshape(1, -1)
+        if kernel:
+            sl = online_trainer.maml_training(rx, tx, sup, j, meta_lr, MAML, return_loss=True)
+        else:
+            sl = torch.stack([meta_train_loop(detector, meta_detector, online_trainer, rx, tx, sup[k], j[k:k + 1], meta_lr, MAML)
+                              for k in range(j.numel())]).to(torch.float32)
+        vtx, vrx = words(mb, "val")
+        rows = torch.tensor([i for i in range(vtx.shape[0]) if i % subframes_in_frame != 0], dtype=torch.int64, device=vtx.device)
+        ser, cnt = _validation(detector, vtx, vrx, snr, gamma, rows, n_symbols, evaluate)
+        if hasattr(online_trainer, "check_status"):
+            online_trainer.check_status()
+        sl = sl.detach().cpu().numpy().astype(np.float32)
+        loss_query = 0.0
+        for v in sl:  # `loss_query +=` (trainer.py:416)
+            loss_query += float(v)
+        if verbose:
+            print(f"Minibatch {mb + 1}, ser - {ser}, loss - {loss_query}")
+        losses.append(loss_query)
+        sers.append(ser)
+        weights.append(_params_copy(detector))
+        step_losses.append(sl)
+        counters.append(cnt)
+        j_used.append(j.cpu().numpy().astype(np.int64))
+    return MetaTrainResult(np.asarray(losses), np.asarray(sers), weights, step_losses,
+                           np.stack(counters) if counters else np.zeros((0, 4), np.int64), j_used)

@@ -221,18 +221,95 @@ class OnlineTrainer:
         self.step += iterations
         return loss
 
-    def _online_training_autograd(self, tx, rx, iterations, batch_idx, full_word, return_loss):
+    def words_kernel_route(self) -> bool:
+        """Does a train_words call run mvn_vnet_train_words_f32?  (A CUDA detector of at most 128 states with use_kernel.)"""
+        return bool(self.use_kernel and self.params[0].is_cuda and self.params[5].numel() <= 128)
+
+    def train_words(self, tx_words: torch.Tensor, rx_words: torch.Tensor, batch_idx: torch.Tensor = None, full_word: bool = False,
+                    return_loss: bool = False, labels: torch.Tensor = None):
+        """One optimizer step per row of tx_words [n, K] / rx_words [n, T], in row order, on the shared exp_avg / exp_avg_sq / step:
+        the inner loop of Trainer.train() (trainer.py:476-479), all n steps in ONE launch (mvn_vnet_train_words_f32).
+        K <= T: the loss of a step runs over positions of the first K symbols -- with use_ecc the reference hands calc_loss the
+        K = 120 message bits against the T = 136 received symbols and select_batch draws from arange(K) (vnet_trainer.py:37-47).
+        full_word=False: batch_idx [n, M] positions in [0, K), or drawn by select_batches(K, n); full_word=True (the whole word,
+        metavnet_trainer.py:41-50) needs K == T.
+        labels: int32 [n, K], the trellis states of tx_words when the caller already has them; None: calculate_states(tx_words).
+        More than 128 states, use_kernel=False and a CPU detector take stock autograd on the same state (words_kernel_route says which).
+        Returns the n losses if return_loss."""
+        if tx_words.dim() != 2 or rx_words.dim() != 2 or tx_words.shape[0] != rx_words.shape[0]:
+            raise ValueError("tx_words [n, K] and rx_words [n, T]")
+        n, K = tx_words.shape
+        T = rx_words.shape[1]
+        if K > T or K < 1:
+            raise ValueError(f"1 <= K <= T: {K} labelled positions against words of {T} symbols")
+        if full_word and K != T:
+            raise ValueError(f"full_word=True needs K == T, got K = {K}, T = {T}")
+        idx = None
+        if not full_word:
+            idx = self.select_batches(K, n) if batch_idx is None else batch_idx
+            if idx.dim() != 2 or idx.shape[0] != n:
+                raise ValueError("batch_idx must be [n_words, M]")
+        return self._train_words(tx_words, rx_words, torch.arange(n, dtype=torch.int32), idx, full_word, return_loss, labels)
+
+    def _train_words(self, tx_words, rx_words, word_of_iter, idx, full_word, return_loss, labels=None):
+        """train_words with the word of every step spelt out: step i trains on row word_of_iter[i] (any order, repeats allowed) with
+        the draws idx[i]; idx None: the whole word."""
+        n, K = tx_words.shape
+        T = rx_words.shape[1]
+        n_iter = word_of_iter.numel()
+        if n_iter == 0:  # no words: no steps, on either route
+            return torch.empty(0, dtype=torch.float32, device=self.params[0].device) if return_loss else None
+        if not self.words_kernel_route():
+            return self._online_training_autograd(tx_words, rx_words, n_iter, idx, full_word, return_loss, word_of_iter=word_of_iter,
+                                                  labels=labels)
+        p = self.params
+        dev = p[0].device
+        _lib.require_gpu_tensor(rx_words, "rx_words")
+        y = rx_words.detach().to(torch.float32).contiguous()
+        if labels is None:
+            labels = calculate_states(self.memory_length, tx_words.detach().to(dev)).reshape(n, K).to(torch.int32).contiguous()
+        elif labels.shape != (n, K) or labels.dtype != torch.int32 or not labels.is_contiguous():
+            raise ValueError("labels: contiguous int32 [n, K]")
+        M = 0
+        if idx is not None:
+            idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+            M = idx.shape[1]
+        woi = word_of_iter.to(device=dev, dtype=torch.int32).contiguous()
+        for t in p:
+            if not t.data.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("ViterbiNet parameters must be contiguous fp32")
+        loss = torch.empty(n_iter, dtype=torch.float32, device=dev) if return_loss else None
+        b1, b2, eps = self.kernel_optimizer_args()
+        with torch.cuda.device(dev):
+            rc = _lib.load().mvn_vnet_train_words_f32(_lib.ptr(y), T, _lib.ptr(labels), K, n, K, _lib.ptr(woi), _lib.ptr(idx), M, n_iter,
+                                                      *[_lib.ptr(t.data) for t in p], _lib.ptr(self.exp_avg),
+                                                      _lib.ptr(self.exp_avg_sq), self.step, self.lr, b1, b2, eps, _lib.ptr(loss),
+                                                      p[5].numel(), _lib.current_stream(dev))
+        _lib.check(rc, "mvn_vnet_train_words_f32")
+        self.step += n_iter
+        return loss
+
+    def _online_training_autograd(self, tx, rx, iterations, batch_idx, full_word, return_loss, word_of_iter=None, labels=None):
         """The same loop on stock PyTorch autograd (run_train_loop, trainer.py:492-505: forward 'train', CrossEntropy over the
         selected samples, backward, Adam on the shared exp_avg / exp_avg_sq / step): the route for memory_length 8 (256 states), whose
-        parameter set does not fit the training kernel's LDS image, and for use_kernel=False.  Same draws as the kernel path (select_batches)."""
+        parameter set does not fit the training kernel's LDS image, and for use_kernel=False.  Same draws as the kernel path (select_batches).
+        word_of_iter (train_words): tx [n, K] / rx [n, T] hold a word per row and iteration `it` trains on row word_of_iter[it], its
+        loss over the first K positions (batch_idx then is given, or full_word); None: the one word of online_training."""
         import torch.nn.functional as F
 
         p = self.params
         dev = p[0].device
         S = p[5].numel()
-        y = rx.detach().to(device=dev, dtype=torch.float32).reshape(1, -1)
-        T = y.shape[1]
-        labels = calculate_states(self.memory_length, tx.detach().to(dev).reshape(1, -1)).reshape(-1).long()
+        if word_of_iter is None:
+            y = rx.detach().to(device=dev, dtype=torch.float32).reshape(1, -1)
+            T = K = y.shape[1]
+            labels = calculate_states(self.memory_length, tx.detach().to(dev).reshape(1, -1)).reshape(1, -1).long()
+        else:
+            y = rx.detach().to(device=dev, dtype=torch.float32)
+            K = tx.shape[1]
+            if labels is None:
+                labels = calculate_states(self.memory_length, tx.detach().to(dev)).reshape(-1, K)
+            labels = labels.to(dev).long()
         idx = None
         if not full_word:
             idx = (self.select_batches(T, iterations) if batch_idx is None else batch_idx.to(dev)).long()
@@ -240,8 +317,9 @@ class OnlineTrainer:
                 raise ValueError("batch_idx must be [iterations, M]")
         losses = []
         for it in range(iterations):
-            logits = self.detector(y, "train").reshape(-1, S)
-            loss = F.cross_entropy(logits, labels) if full_word else F.cross_entropy(logits[idx[it]], labels[idx[it]])
+            w = 0 if word_of_iter is None else int(word_of_iter[it])
+            logits = self.detector(y[w:w + 1], "train").reshape(-1, S)[:K]
+            loss = F.cross_entropy(logits, labels[w]) if full_word else F.cross_entropy(logits[idx[it]], labels[w][idx[it]])
             self.optimizer_step(torch.autograd.grad(loss, p))
             if return_loss:
                 losses.append(loss.detach())
