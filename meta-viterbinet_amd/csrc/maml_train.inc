@@ -142,7 +142,7 @@ __device__ __forceinline__ void hv_chunk(const float *p, const float *v, float *
         const float x = A.pr[n * kDlStride + s];
         const float mx = sample_allreduce<true>(x, S);
         const float sum = sample_allreduce<false>(expf(x - mx), S);
-        const float prob = expf(x - (mx + logf(sum)));
+        const float prob = expf((x - mx) - logf(sum));  // torch's log_softmax order: rounds at |x - max|, not at |max| (DESIGN 5.10.1)
         const float ro = A.Rdo[n * kDlStride + s];
         const float dot = sample_allreduce<false>(prob * ro, S);
         const bool live = n < nc;
@@ -523,11 +523,11 @@ __device__ __forceinline__ void hv_chunk_states(const float *p, const float *v, 
         for (int k = 0; k < NK; ++k) sum += expf(x[k] - mx);
         sum = sample_allreduce<false>(sum, 32);
         sum += __shfl_xor(sum, 32);
-        const float lse = mx + logf(sum);
+        const float lg = logf(sum);
         float dot = 0.0f;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
-            prob[k] = expf(x[k] - lse);
+            prob[k] = expf((x[k] - mx) - lg);
             dot += prob[k] * ro[k];
         }
         dot = sample_allreduce<false>(dot, 32);

@@ -391,13 +391,14 @@ __device__ __forceinline__ void grad_chunk(const float *p, float *g, const Train
             for (int k = 0; k < NK; ++k) sum += expf(x[k] - mx);
             sum = sample_allreduce<false>(sum, 32);
             sum += __shfl_xor(sum, 32);
-            const float lse = mx + logf(sum);
+            const float lg = logf(sum);  // log_softmax = (x - max) - log(sum), torch's order: rounds at |x - max|, not at |max|
             const int label = lab[n];
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const bool hit = lane_ + 64 * k == label;
-                if (hit) red[n] = n < nc ? lse - x[k] : 0.0f;
-                dl[n * DLS + lane_ + 64 * k] = n < nc ? (expf(x[k] - lse) - (hit ? 1.0f : 0.0f)) * inv_n : 0.0f;
+                const float ls = (x[k] - mx) - lg;
+                if (hit) red[n] = n < nc ? 0.0f - ls : 0.0f;
+                dl[n * DLS + lane_ + 64 * k] = n < nc ? (expf(ls) - (hit ? 1.0f : 0.0f)) * inv_n : 0.0f;
             }
         }
     } else
@@ -408,11 +409,12 @@ __device__ __forceinline__ void grad_chunk(const float *p, float *g, const Train
         const int n = tid / S, s = tid % S;
         const float x = dl[n * DLS + s];
         const float mx = sample_allreduce<true>(x, S);
-        const float sum = sample_allreduce<false>(expf(x - mx), S);
-        const float lse = mx + logf(sum);
+        const float xm = x - mx;
+        const float sum = sample_allreduce<false>(expf(xm), S);
+        const float ls = xm - logf(sum);  // log_softmax in torch's order: rounds at |x - max|, not at |max| (DESIGN 5.10.1)
         const bool hit = s == lab[n];
-        if (hit) red[n] = n < nc ? lse - x : 0.0f;
-        dl[n * DLS + s] = n < nc ? (expf(x - lse) - (hit ? 1.0f : 0.0f)) * inv_n : 0.0f;
+        if (hit) red[n] = n < nc ? 0.0f - ls : 0.0f;
+        dl[n * DLS + s] = n < nc ? (expf(ls) - (hit ? 1.0f : 0.0f)) * inv_n : 0.0f;
     }
     }
     TRAIN_STAMP_WAVE(3);
