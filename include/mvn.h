@@ -217,12 +217,14 @@ int mvn_count_errors(const float *dec, int64_t dec_ld, const float *tx, int64_t 
  *   samples every iteration (metavnet_trainer.py:41-50);
  *   W1..b3: parameters, updated in place; adam_m/adam_v: [P] exp_avg / exp_avg_sq in parameter order
  *   (P = 250 + 50*100 + 51*S), updated in place; step0 = Adam steps already taken;
- *   loss_out [n_iter] or NULL.  S <= 128 (64 / 128 states: one workgroup per trial, the optimizer's moments stay in global
- *   memory).  fp32; agrees with torch autograd + Adam to rounding, not bitwise.
+ *   loss_out [n_iter] or NULL.  S <= 256 (64 / 128 / 256 states: one workgroup per trial, the optimizer's moments stay in
+ *   global memory; 256 states -- online_train_kernel<256, false>, this call, its _ws_ form and mvn_vnet_train_words_states_f32 only --
+ *   also keep W3's gradient out of LDS, in the registers that accumulate it).  fp32; agrees with torch autograd + Adam to
+ *   rounding, not bitwise.
  * The trainer's other optimizers (deep_learning_setup, trainer.py:163-175) ride on the same arguments: beta1 = MVN_BETA1_RMSPROP
  * runs torch.optim.RMSprop's update (alpha = beta2, eps; square average in adam_v, adam_m untouched; torch's defaults: no
  * momentum, not centered), beta1 = MVN_BETA1_SGD torch.optim.SGD's (p -= lr g; adam_m / adam_v untouched).  The same holds for
- * the _ws_ and _trials_ forms of this call; the meta-learning calls below take Adam only and return MVN_E_DIMS for beta1 < 0.
+ * the _ws_ and _trials_ forms of this call (the _trials_ form: S <= 128); the meta-learning calls below take Adam only and return MVN_E_DIMS for beta1 < 0.
  */
 #define MVN_BETA1_RMSPROP (-1.0f)
 #define MVN_BETA1_SGD (-2.0f)
@@ -237,7 +239,8 @@ int mvn_vnet_online_train_f32(const float *y, const int32_t *labels, int32_t T, 
  * device memory, 16-byte aligned, used for the gradient exchange between the workgroups (contents irrelevant before and
  * after; must not be shared by calls that may run concurrently).  Results are bit-identical to
  * mvn_vnet_online_train_f32, which also serves every case this form does not (minibatch iterations, words of at most
- * 32 symbols or more than 1024, workspace NULL or too small, MVN_TRAIN_GROUPS=0 in the environment).
+ * 32 symbols or more than 1024, workspace NULL or too small, MVN_TRAIN_GROUPS=0 in the environment).  S <= 256; above 32 states
+ * every call runs on the one workgroup and mvn_vnet_train_workspace_bytes is 0.
  */
 size_t mvn_vnet_train_workspace_bytes(int32_t n_states);
 /* status: device int32[1] or NULL.  The workgroups of this form meet at a device-wide barrier whose wait is bounded (a launch
@@ -264,8 +267,8 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
  *   drawn twice counts twice), or NULL / M == 0: all K positions in every iteration.
  *   W1..b3, adam_m / adam_v [P], step0, lr, beta1 (Adam, or the MVN_BETA1_RMSPROP / MVN_BETA1_SGD tags), beta2, eps, loss_out
  *   [n_iter] or NULL, S <= 128: as mvn_vnet_online_train_f32.
- * One 1024-thread workgroup (online_train_words_kernel<S or 0>: the same chunk code, sums and optimizer update as
- * online_train_kernel<S, false>); with word_of_iter[i] naming rows that hold the same word the results are bit for bit those
+ * One 1024-thread workgroup (online_train_words_kernel<S or 0>: the same chunk
+ * code, sums and optimizer update as online_train_kernel<S, false>); with word_of_iter[i] naming rows that hold the same word the results are bit for bit those
  * of mvn_vnet_online_train_f32 on that word.  No workspace: a whole-word iteration also runs on the one workgroup.
  * Returns, in this order, before anything is launched: MVN_E_DIMS (n_iter < 0, n_words < 1, K < 1, K above a row stride, a row
  * stride above INT32_MAX, M < 0, M > K, step0 < 0), MVN_E_STATES (S above 128 or not a power of two), MVN_OK for n_iter == 0
@@ -277,6 +280,19 @@ int mvn_vnet_train_words_f32(const float *y, int64_t y_ld, const int32_t *labels
                              const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1, float *b1,
                              float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0, float lr,
                              float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream);
+
+/*
+ * mvn_vnet_train_words_f32 for every state count the single-trial online kernels serve, S <= 256: the same arguments, the same
+ * checks and codes in the same order (MVN_E_STATES: S above 256 or not a power of two), the same launch and bits up to 128 states;
+ * at 256 states (channel memory 8) online_train_words_states256_kernel, the word-axis twin of online_train_kernel<256, false> (W3's
+ * gradient in the registers that accumulate it).  A call of its own, like mvn_vnet_byword_step_states_f32 beside
+ * mvn_vnet_byword_step_f32: mvn_vnet_train_words_f32 keeps answering MVN_E_STATES at 256 states, which its callers may rely on.
+ * (Added without a bump of MVN_ABI_VERSION, like the by-word steps.)
+ */
+int mvn_vnet_train_words_states_f32(const float *y, int64_t y_ld, const int32_t *labels, int64_t labels_ld, int64_t n_words, int32_t K,
+                                    const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1,
+                                    float *b1, float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0,
+                                    float lr, float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream);
 
 /*
  * n_steps online meta-learning steps of Meta-ViterbiNet in ONE launch: Trainer.meta_train_loop
@@ -384,6 +400,8 @@ int mvn_vnet_maml_train_states_trials_f32(const mvn_train_trial_t *trials, int32
  * name (HOST pointer) receives e.g. "maml_train_kernel<16, true> 1x176" or "online_train_groups_kernel<16, true> 5x48 in 2
  * launches one XCD per trial" (workgroups per trial x trials per launch; "one XCD per trial": the grid that places a trial's
  * workgroups on one XCD so that their gradient exchange stays in its L2 -- MVN_TRAIN_XCD=0 keeps the (groups, trials) grid).
+ * S <= 128; kind 0 with R = 0 also answers at S = 256 ("online_train_kernel<256, false> 1x1", the form mvn_vnet_online_train_f32 and
+ * its _ws_ form launch; mvn_vnet_train_words_states_f32 launches its word-axis twin).
  * Returns 0, MVN_E_DIMS, MVN_E_STATES or MVN_E_NULL.
  */
 int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_W, int32_t S, size_t workspace_bytes, char *name,
@@ -392,6 +410,10 @@ int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_
  * alike) at n_states; 0 where the kind does not serve that state count (kind 0, 1, 2: up to 128 states) or for another kind.
  * The counterpart of mvn_lstm_train_lds_bytes: always within one CU's 163 840 bytes. */
 size_t mvn_vnet_train_lds_bytes(int32_t kind, int32_t n_states);
+/* The dynamic LDS (bytes) of the single-trial online-training kernels (online_train_kernel<SC, false> and the word axis) at every
+ * state count they serve, 2 ... 256: mvn_vnet_train_lds_bytes(0, n_states) up to 128 states, 158 668 at 256 (parameters, the
+ * gradient vector without dW3, a chunk's images); 0 for any other n_states.  Within one CU's 163 840 bytes. */
+size_t mvn_vnet_online_train_lds_bytes(int32_t n_states);
 
 /*
  * One block step of Trainer.eval_by_word (python_code/trainers/trainer.py:292-316 and the buffer entry of :322-324) for R

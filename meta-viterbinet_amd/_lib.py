@@ -54,6 +54,8 @@ SIGNATURES = {
                                       ctypes.c_size_t, _vp, _vp]),
     "mvn_vnet_train_words_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32] + [_vp] * 8 +
                                  [_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i32, _vp]),
+    "mvn_vnet_train_words_states_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32] + [_vp] * 8 +
+                                        [_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i32, _vp]),
     "mvn_vnet_maml_train_f32": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32] + [_vp] * 8 +
                                 [_i64, ctypes.c_float, _i32] + [ctypes.c_float] * 4 + [_vp, _i32, _vp]),
     "mvn_vnet_maml_train_ws_f32": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32] + [_vp] * 8 +
@@ -66,6 +68,7 @@ SIGNATURES = {
                                               [_i32, _vp]),
     "mvn_vnet_train_kernel_name": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.c_size_t, ctypes.c_char_p, _i32]),
     "mvn_vnet_train_lds_bytes": (ctypes.c_size_t, [_i32, _i32]),
+    "mvn_vnet_online_train_lds_bytes": (ctypes.c_size_t, [_i32]),
     "mvn_vnet_byword_step_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_vnet_byword_step_max_symbols": (_i32, [_i32]),
     "mvn_vnet_byword_step_states_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),

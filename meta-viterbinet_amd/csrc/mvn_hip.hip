@@ -1069,8 +1069,10 @@ struct TrainPlan {
 TrainPlan plan_train(int kind, bool many, int R, int T, int M_or_W, int S, bool has_workspace, size_t workspace_bytes) {
     TrainPlan p = {};
     // compile-time state counts: 16; 32 for one trial (R trials at S = 32 take the run-time form); 64 / 128, the single-workgroup
-    // forms of one trial (online_train_kernel, maml_train_kernel <64 | 128, false>); 0 = run-time
-    p.sc = S == 16 || (S == 32 && !many) || S == 64 || S == 128 ? S : 0;
+    // forms of one trial (online_train_kernel, maml_train_kernel <64 | 128, false>); 256: one trial's online training only
+    // (online_train_kernel<256, false> and the word axis' online_train_words_states256_kernel; the entry points refuse the rest);
+    // 0 = run-time
+    p.sc = S == 16 || (S == 32 && !many) || S == 64 || S == 128 || S == 256 ? S : 0;
     // one workgroup per chunk of the largest pass.  Minibatch iterations are one chunk: nothing to spread; 64 / 128 states: one workgroup
     int groups = S > 32 ? 0 : kind == 0 ? (M_or_W > 0 ? 0 : online_groups(T)) : maml_groups(T, M_or_W, kind == 2);
     const int cus = current_device_cus();
@@ -1101,6 +1103,7 @@ int dispatch_states(int sc, Launch launch) {
     if (sc == 32) return launch(std::integral_constant<int, 32>{});
     if (sc == 64) return launch(std::integral_constant<int, 64>{});
     if (sc == 128) return launch(std::integral_constant<int, 128>{});
+    if (sc == 256) return launch(std::integral_constant<int, 256>{});
     return launch(std::integral_constant<int, 0>{});
 }
 
@@ -1164,6 +1167,14 @@ int launch_train(bool maml, const mvn_train_trial_t &one, const mvn_train_trial_
     const auto meta = std::tuple_cat(std::make_tuple(T, M_or_W, meta_lr, second_order), adam);
     return dispatch_states(c.plan.sc, [&](auto sc) -> int {
         constexpr int SC1 = decltype(sc)::value;    // one workgroup per trial: 64 / 128 states have their own forms
+        if constexpr (SC1 == 256) {  // one trial's online training, nothing else (the entry points refuse it before they get here)
+            if (maml || many || c.plan.form != kTrainPerTrial) return MVN_E_STATES;
+            if (words)
+                return train_run(online_train_words_states256_kernel, online_train_words_states256_kernel, c, kTrainThreads,
+                                 std::tuple_cat(std::make_tuple(T, M_or_W, words->ld_y, words->ld_lab), adam));
+            return train_run(online_train_kernel<256, false>, online_train_kernel<256, false>, c, kTrainThreads,
+                             std::tuple_cat(std::make_tuple(T, M_or_W), adam));
+        } else {
         constexpr int SC1M = SC1 == 32 ? 0 : SC1;   // (the run-time form for R trials at 32 states)
         constexpr int SC = SC1 > 32 ? 0 : SC1;      // the chunked kernels and R meta-learning trials: up to 32 states (plan_train, the entry point)
         constexpr int SCM = SC == 32 ? 0 : SC;
@@ -1184,6 +1195,7 @@ int launch_train(bool maml, const mvn_train_trial_t &one, const mvn_train_trial_
             return train_run(pair, pair, c, kTrainThreads2, online);
         }
         return train_run(online_train_kernel<SC1M, true>, online_train_kernel<SC1, false>, c, kTrainThreads, online);
+        }
     });
 }
 
@@ -1745,7 +1757,8 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
                                  float *loss_out, int32_t S, void *workspace, size_t workspace_bytes, int32_t *status,
                                  mvn_stream_t stream) {
     if (T < 1 || n_iter < 0 || step0 < 0 || (batch_idx && M < 1)) return MVN_E_DIMS;
-    if (!valid_states(S) || S > 128) return MVN_E_STATES;  // parameters + gradient + a chunk must fit the 160-KB LDS
+    // parameters + gradient + a chunk must fit the 160-KB LDS (at 256 states: with W3's gradient in registers)
+    if (!valid_states(S) || S > 256) return MVN_E_STATES;
     if (n_iter == 0) return MVN_OK;
     if (!y || !labels || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !adam_m || !adam_v) return MVN_E_NULL;
     const mvn_train_trial_t d = train_trial(y, labels, batch_idx, nullptr, {W1, b1, W2, b2, W3, b3}, adam_m, adam_v, loss_out, status,
@@ -1754,13 +1767,15 @@ int mvn_vnet_online_train_ws_f32(const float *y, const int32_t *labels, int32_t 
                         (hipStream_t)stream);
 }
 
-int mvn_vnet_train_words_f32(const float *y, int64_t y_ld, const int32_t *labels, int64_t labels_ld, int64_t n_words, int32_t K,
-                             const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1, float *b1,
-                             float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0, float lr,
-                             float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream) {
+// The word axis' two entry points: one check, one launch.  max_states: 128 for mvn_vnet_train_words_f32 (whose answer at 256 states,
+// MVN_E_STATES, its callers may rely on), 256 for mvn_vnet_train_words_states_f32.
+static int train_words_run(const float *y, int64_t y_ld, const int32_t *labels, int64_t labels_ld, int64_t n_words, int32_t K,
+                           const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1, float *b1,
+                           float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0, float lr,
+                           float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream, int max_states) {
     if (n_iter < 0 || n_words < 1 || K < 1 || y_ld < K || labels_ld < K || M < 0 || M > K || step0 < 0) return MVN_E_DIMS;
     if (y_ld > INT32_MAX || labels_ld > INT32_MAX) return MVN_E_DIMS;  // (the kernel takes the row strides as 32-bit arguments)
-    if (!valid_states(S) || S > 128) return MVN_E_STATES;
+    if (!valid_states(S) || S > max_states) return MVN_E_STATES;
     if (n_iter == 0) return MVN_OK;
     if (!y || !labels || !word_of_iter || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !adam_m || !adam_v) return MVN_E_NULL;
     // batch_idx == NULL or M == 0: all K positions of the word in every iteration (batch_idx is not read)
@@ -1771,9 +1786,30 @@ int mvn_vnet_train_words_f32(const float *y, int64_t y_ld, const int32_t *labels
     return launch_train(false, d, nullptr, 1, K, idx ? M : 0, 0.0f, 0, lr, beta1, beta2, eps, S, nullptr, 0, (hipStream_t)stream, &words);
 }
 
+int mvn_vnet_train_words_f32(const float *y, int64_t y_ld, const int32_t *labels, int64_t labels_ld, int64_t n_words, int32_t K,
+                             const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1, float *b1,
+                             float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0, float lr,
+                             float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream) {
+    return train_words_run(y, y_ld, labels, labels_ld, n_words, K, word_of_iter, batch_idx, M, n_iter, W1, b1, W2, b2, W3, b3, adam_m,
+                           adam_v, step0, lr, beta1, beta2, eps, loss_out, S, stream, 128);
+}
+
+int mvn_vnet_train_words_states_f32(const float *y, int64_t y_ld, const int32_t *labels, int64_t labels_ld, int64_t n_words, int32_t K,
+                                    const int32_t *word_of_iter, const int32_t *batch_idx, int32_t M, int32_t n_iter, float *W1,
+                                    float *b1, float *W2, float *b2, float *W3, float *b3, float *adam_m, float *adam_v, int64_t step0,
+                                    float lr, float beta1, float beta2, float eps, float *loss_out, int32_t S, mvn_stream_t stream) {
+    return train_words_run(y, y_ld, labels, labels_ld, n_words, K, word_of_iter, batch_idx, M, n_iter, W1, b1, W2, b2, W3, b3, adam_m,
+                           adam_v, step0, lr, beta1, beta2, eps, loss_out, S, stream, 256);
+}
+
 size_t mvn_vnet_train_lds_bytes(int32_t kind, int32_t S) {
     if (kind < 0 || kind > 2 || !valid_states(S) || S > 128) return 0;
     return kind == 0 ? online_train_lds_bytes(S) : maml_train_lds_floats(S) * sizeof(float);
+}
+
+size_t mvn_vnet_online_train_lds_bytes(int32_t S) {
+    if (!valid_states(S) || S > 256) return 0;
+    return online_train_lds_bytes(S);
 }
 
 int mvn_vnet_online_train_trials_f32(const mvn_train_trial_t *trials, int32_t R, int32_t T, int32_t M, float lr, float beta1,
@@ -1840,8 +1876,8 @@ int mvn_vnet_maml_train_states_trials_f32(const mvn_train_trial_t *trials, int32
 int mvn_vnet_train_kernel_name(int32_t kind, int32_t R, int32_t T, int32_t M_or_W, int32_t S, size_t workspace_bytes, char *name,
                                int32_t name_len) {
     if (kind < 0 || kind > 2 || R < 0 || T < 1 || M_or_W < 0 || (kind > 0 && M_or_W < 1)) return MVN_E_DIMS;
-    // (the trial-batched meta-learning entry point stops at 32 states)
-    if (!valid_states(S) || S > 128 || (kind > 0 && R > 0 && S > 32)) return MVN_E_STATES;
+    // (the trial-batched meta-learning entry point stops at 32 states; 256 states: one trial's online training only)
+    if (!valid_states(S) || S > 256 || (S > 128 && (kind > 0 || R > 0)) || (kind > 0 && R > 0 && S > 32)) return MVN_E_STATES;
     if (!name || name_len < 1) return MVN_E_NULL;
     const bool many = R > 0;
     const TrainPlan p = plan_train(kind, many, many ? R : 1, T, M_or_W, S, workspace_bytes > 0, workspace_bytes);

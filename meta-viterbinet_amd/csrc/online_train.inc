@@ -25,6 +25,9 @@ constexpr int kTrainChunk = 32;  // samples processed per pass (select_batch's m
 constexpr int kH1Ld = kH1 + 2;      // h1 / dz1 images and W2's rows in the LDS parameter vectors
 constexpr int kZ2Stride = kH2 + 4;  // 54
 constexpr int kDlStride = 34;
+// Up to this many states W3's gradient lies in the LDS gradient vector g[]; above (256) it stays in registers (grad_chunk, SCC = 256)
+// and g[] ends with db3 where dW3 would begin.
+constexpr int kGradW3InLdsStates = 128;
 
 struct TrainLayout {  // offsets (floats) of the six parameter arrays inside one LDS vector [P], torch order, W2's rows padded
     int w1, b1, w2, b2, w3, b3, P, P4, Pflat;  // Pflat: length of the unpadded vector (the Adam moments in global memory)
@@ -276,13 +279,20 @@ struct NoHook {
 // that know the state count change shape: a dlogits row is SCC + 2 floats (the arena must have been built with that stride), the
 // softmax takes a whole wave per sample (SCC / 64 states per lane), dz2 contracts over SCC / 4 k-steps, and the SCC / 16 x 4 tiles
 // of dW3 are looped over by the eight waves that took one each.  1024-thread workgroups only.
+// SCC = 256: parameters, gradient and arena together are 210 KB, so W3's gradient (51 KB) has no place in g[] (whose b3 then follows
+// b2: kGradW3InRegs below) -- it stays in the MFMA accumulators that compute it.  Its 16 x 4 tiles are dealt four to a wave, wave w
+// owning tiles (w >> 2) + 4 j, j = 0..3, of column tile w & 3 (they share the relu(z2) operand), 16 VGPRs `dw3` that the caller keeps
+// across the chunks of a pass and hands to apply_dw3_from_regs afterwards.  A chunk adds its tile to the accumulator in the order the
+// LDS form adds it to g[] (FIRST: overwrites), one owner per element: the same bits on every run.  The 32 logits tiles go two to a wave.
 template <int ROWS, bool FIRST, int NT = kTrainThreads, int SCC = 0, class Hook = NoHook, class Closing = NoHook>
 __device__ __forceinline__ void grad_chunk(const float *p, float *g, const TrainLayout &L, const ChunkArena<kTrainChunk> &A, int nc,
-                                           float inv_n, int S, Hook idle_hook = Hook(), Closing closing_hook = Closing()) {
+                                           float inv_n, int S, Hook idle_hook = Hook(), Closing closing_hook = Closing(),
+                                           f32x4 *dw3 = nullptr) {
     constexpr bool first = FIRST;
     constexpr bool BIG = SCC > 32;
+    constexpr bool W3REG = SCC > kGradW3InLdsStates;
     constexpr int DLS = BIG ? SCC + 2 : kDlStride;  // floats per dlogits row
-    static_assert(!BIG || (NT == kTrainThreads && SCC % 64 == 0), "64 or 128 states on 16 waves");
+    static_assert(!BIG || (NT == kTrainThreads && SCC % 64 == 0), "64, 128 or 256 states on 16 waves");
     static_assert(NT == kTrainThreads || 2 * NT == kTrainThreads, "16 waves, or 8 taking two roles each");
     constexpr int NV = kTrainThreads / NT;  // passes of the physical threads over the 1024 virtual ones
 #define MVN_VIRTUAL_WAVES _Pragma("unroll 1") for (int vpass = 0; vpass < NV; ++vpass)
@@ -354,6 +364,19 @@ __device__ __forceinline__ void grad_chunk(const float *p, float *g, const Train
     TRAIN_STAMP_WAVE(1);
     __syncthreads();
     TRAIN_STAMP(2);
+    if constexpr (W3REG) {  // RT x 16 logits tiles on 16 waves: tiles wave0 and (RT = 2) wave0 + 16
+#pragma unroll 1
+        for (int t = wave0; t < RT * (SCC / 16); t += kTrainThreads / 64) {
+            const int tm = t % RT, ts = t / RT;
+            const int s = 16 * ts + li;
+            const float bias = p[L.b3 + s];
+            __builtin_amdgcn_sched_barrier(0);
+            const f32x4 acc = lds_tile_mfma<kK3Steps, 1, 1, true, false>(z2 + (16 * tm + li) * kZ2Stride + lq,
+                                                                         p + L.w3 + (16 * ts + li) * kH2 + lq);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dl[(16 * tm + 4 * lq + r) * DLS + s] = acc[r] + bias;
+        }
+    } else
     MVN_VIRTUAL_WAVES {
     MVN_VIRTUAL_IDS;
     (void)tid;
@@ -439,7 +462,7 @@ __device__ __forceinline__ void grad_chunk(const float *p, float *g, const Train
         if (k < kH2)
 #pragma unroll
             for (int r = 0; r < 4; ++r) dz2[e0 + r * kZ2Stride] = zv[r] > 0.0f ? acc[r] : 0.0f;
-    } else if (wave >= 8 && wave < 8 + 4 * TS) {  // dW3 [S][50] += dlogits^T [S][ROWS] . relu(z2) [ROWS][50]: TS x 4 tiles
+    } else if (!W3REG && wave >= 8 && wave < 8 + 4 * TS) {  // dW3 [S][50] += dlogits^T [S][ROWS] . relu(z2) [ROWS][50]: TS x 4 tiles
         // (up to 32 states: a tile per wave; SCC: waves 8..15 take tiles wave - 8, wave, wave + 8, ...)
 #pragma unroll 1
         for (int t = wave - 8; t < 4 * TS; t += 8) {
@@ -454,6 +477,17 @@ __device__ __forceinline__ void grad_chunk(const float *p, float *g, const Train
             }
         }
     }
+    if constexpr (W3REG) {  // every wave: its four tiles of dW3, into the accumulators (bit for bit the tiles lds_tile_mfma gives)
+        const int ts0 = wave >> 2, tn = wave & 3;
+        const float *const a0 = dl + rk * DLS + 16 * ts0 + li;
+        const float *const al[4] = {a0, a0 + 64, a0 + 128, a0 + 192}, *const bl[1] = {z2 + rk * kZ2Stride + 16 * tn + li};
+        f32x4 acc[4][1];
+        lds_block_mfma<ROWS / 4, DLS, kZ2Stride, false, true, true, 4, 1>(al, bl, acc);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dw3[j][r] = first ? acc[j][0][r] : dw3[j][r] + acc[j][0][r];
+    }
     // db3 (wave 15) and the loss sum (wave 14): 32 operands each, all in flight at once -- one LDS round trip instead of the
     // five the compiler makes of the plain loop (this wave was the last to reach the barrier by 1 000 cycles)
     if (wave == 15 && lane < S) {
@@ -466,7 +500,8 @@ __device__ __forceinline__ void grad_chunk(const float *p, float *g, const Train
             float acc = 0.0f;
 #pragma unroll
             for (int n = 0; n < ROWS; ++n) acc += dv[n];
-            g[L.b3 + s] = first ? acc : g[L.b3 + s] + acc;
+            const int e = (W3REG ? L.w3 : L.b3) + s;  // (db3 follows db2 where dW3 is not in g[])
+            g[e] = first ? acc : g[e] + acc;
         }
     } else if (wave == 14 && lane == 0) {  // rows n >= nc hold 0
         float rv[ROWS];
@@ -676,6 +711,46 @@ __device__ __forceinline__ void adam4(float4 &p4, float4 &m4, float4 &v4, const 
     adam1(p4.w, m4.w, v4.w, gr4.w, beta1, beta2, eps, step_size, inv_sqrt_bc2);
 }
 
+// The optimizer step of W3 at 256 states, from the accumulators grad_chunk left its gradient in: lane (li, lq) of wave w holds
+// dW3[16 ((w >> 2) + 4 j) + 4 lq + r][16 (w & 3) + li] in dw3[j][r] (the MFMA's output layout).  W3 is in LDS, its moments are
+// elements w3_flat + s * 50 + k of the flat vectors in global memory; the same adam1 per element as everywhere else.
+__device__ __forceinline__ void apply_dw3_from_regs(float *p, const TrainLayout &L, const f32x4 *dw3, float *__restrict__ adam_m,
+                                                    float *__restrict__ adam_v, float beta1, float beta2, float eps, float step_size,
+                                                    float inv_sqrt_bc2) {
+    // (the thread index is made opaque, as in grad_chunk: the 48 element offsets below are then recomputed in every iteration; left
+    // alone they are hoisted out of the iteration loop, spilled, and reloaded from scratch here each time)
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    const int lane = t & 63, wave = t >> 6, li = lane & 15, lq = lane >> 4;
+    const int k = 16 * (wave & 3) + li, w3_flat = L.w3 - kH2 * (kH1Ld - kH1);
+    const bool live = k < kH2;  // (the fourth column tile holds units 48, 49 only; its other lanes load element 0 and store nothing)
+#pragma unroll
+    for (int j0 = 0; j0 < 4; j0 += 2) {  // two tiles at a time: 16 global loads in flight together (all four: the registers spill)
+        float me[2][4], ve[2][4], pe[2][4];
+        unsigned o[2][4];  // (unsigned: a 32-bit offset from the uniform base pointer, no 64-bit address per load)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                o[j][r] = live ? (unsigned)((16 * ((wave >> 2) + 4 * (j0 + j)) + 4 * lq + r) * kH2 + k) : 0u;
+                me[j][r] = adam_m[(unsigned)w3_flat + o[j][r]];
+                ve[j][r] = adam_v[(unsigned)w3_flat + o[j][r]];
+                pe[j][r] = p[(unsigned)L.w3 + o[j][r]];
+            }
+        __builtin_amdgcn_sched_barrier(0);
+        if (live)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    adam1(pe[j][r], me[j][r], ve[j][r], dw3[j0 + j][r], beta1, beta2, eps, step_size, inv_sqrt_bc2);
+                    p[(unsigned)L.w3 + o[j][r]] = pe[j][r];
+                    adam_m[(unsigned)w3_flat + o[j][r]] = me[j][r];
+                    adam_v[(unsigned)w3_flat + o[j][r]] = ve[j][r];
+                }
+    }
+}
+
 // Staging of a trial's six parameter arrays (torch layout, six separate pointers) into / out of the LDS vector
 template <int NT = kTrainThreads>
 __device__ __forceinline__ void load_params(float *p, const TrainLayout &L, int S, const float *const (&src)[6]) {
@@ -772,9 +847,24 @@ __global__ __launch_bounds__(kTrainThreads, 1) void online_train_words_kernel(
 #undef MVN_TRAIN_WORDS
 }
 
+// 256 states on the word axis.  Its own name, not online_train_words_kernel<256>: that template's instantiations are the five
+// state constants the trial axis shares, and this form has no trial-batched twin.
+__global__ __launch_bounds__(kTrainThreads, 1) void online_train_words_states256_kernel(
+    const mvn_train_trial_t one, const mvn_train_trial_t *__restrict__ many, int T, int M, int ld_y, int ld_lab, float lr, float beta1,
+    float beta2, float eps, int S_rt, int lds_floats) {
+    constexpr int SC = 256;
+    constexpr bool MANY = false;
+    constexpr int NT = kTrainThreads;
+#define MVN_TRAIN_WORDS 1
+#include "online_train_body.inc"
+#undef MVN_TRAIN_WORDS
+}
+
 inline size_t online_train_lds_floats(int S) {
     const TrainLayout L = train_layout(S);
     // + 64: operand rows read past the last activation image (discarded output columns) stay inside the allocation
+    // 256 states: the gradient vector without dW3 (registers: grad_chunk) -- 158 668 bytes of the CU's 163 840
+    if (S > kGradW3InLdsStates) return (size_t)2 * L.P4 - (size_t)S * kH2 + ChunkArena<kTrainChunk>::floats(S + 2) + 64;
     if (S > 32) return (size_t)2 * L.P4 + ChunkArena<kTrainChunk>::floats(S + 2) + 64;  // (moments in global memory)
     return (size_t)4 * L.P4 + ChunkArena<kTrainChunk>::kFloats + 64;
 }

@@ -21,12 +21,18 @@
     // 1024-thread workgroup with the moments in global memory, like the 512-thread form
     constexpr int SCC = SC > 32 ? SC : 0;  // grad_chunk's compile-time state count above 32
     constexpr bool kMomentsInLds = NT == kTrainThreads && SC <= 32;
-    static_assert(SC <= 32 || NT == kTrainThreads, "64 / 128 states: 1024-thread workgroups");
+    static_assert(SC <= 32 || NT == kTrainThreads, "64 / 128 / 256 states: 1024-thread workgroups");
+    // SC = 256: parameters 73.6 KB, arena 62.3 KB -- the gradient vector goes without dW3 (22.4 KB instead of 73.6), which lives in
+    // the 16 accumulator registers dw3 of every thread across a pass (grad_chunk) and meets Adam there (apply_dw3_from_regs)
+    constexpr bool kW3Regs = SC > kGradW3InLdsStates;
+    static_assert(!kW3Regs || !MANY, "256 states: one trial");
+    f32x4 dw3[kW3Regs ? 4 : 1];
     float *p = smem;       // parameters
     float *g = p + L.P4;   // gradient accumulators
     float *am = g + L.P4;  // Adam exp_avg    } (NT = 1024 up to 32 states; otherwise they stay in global memory)
     float *av = am + L.P4; // Adam exp_avg_sq }
-    const ChunkArena<kTrainChunk> A(kMomentsInLds ? av + L.P4 : g + L.P4, NT != kTrainThreads, SCC ? SCC + 2 : kDlStride);
+    const ChunkArena<kTrainChunk> A(kMomentsInLds ? av + L.P4 : g + (kW3Regs ? L.P4 - SC * kH2 : L.P4), NT != kTrainThreads,
+                                    SCC ? SCC + 2 : kDlStride);
     const int tid = threadIdx.x;
 
     MVN_CLEAR_LDS_LOAD_PARAMS(NT, p);
@@ -124,9 +130,9 @@
         // first chunk, a further full chunk, a further chunk of at most 16 samples
         for (int c0 = 0; c0 < n_total; c0 += kTrainChunk) {
             const int nc = n_total - c0 < kTrainChunk ? n_total - c0 : kTrainChunk;
-            if (c0 == 0) grad_chunk<kTrainChunk, true, NT, SCC>(p, g, L, A, nc, inv_n, S, bias_corrections, stage_chunk);
-            else if (nc <= 16) grad_chunk<16, false, NT, SCC>(p, g, L, A, nc, inv_n, S, NoHook(), stage_chunk);
-            else grad_chunk<kTrainChunk, false, NT, SCC>(p, g, L, A, nc, inv_n, S, NoHook(), stage_chunk);
+            if (c0 == 0) grad_chunk<kTrainChunk, true, NT, SCC>(p, g, L, A, nc, inv_n, S, bias_corrections, stage_chunk, kW3Regs ? dw3 : nullptr);
+            else if (nc <= 16) grad_chunk<16, false, NT, SCC>(p, g, L, A, nc, inv_n, S, NoHook(), stage_chunk, kW3Regs ? dw3 : nullptr);
+            else grad_chunk<kTrainChunk, false, NT, SCC>(p, g, L, A, nc, inv_n, S, NoHook(), stage_chunk, kW3Regs ? dw3 : nullptr);
         }
         const float step_size = A.red[kTrainChunk + 1], inv_sqrt_bc2 = A.red[kTrainChunk + 2];
         if constexpr (MVN_ABL(7)) {
@@ -148,6 +154,35 @@
                 V[e4b] = vb;
                 P[e4b] = pb;
             }
+        } else if constexpr (kW3Regs) {  // as below for everything but W3: element i < w3_flat of the flat vectors, then b3
+            // 5 506 elements, six per thread, all their loads in flight at once.  An element past the end takes element 0's place
+            // in the loads (no branch around a load: the compiler otherwise waits for each on its own) and stores nothing.
+            constexpr int kW3 = SC * kH2, kW3Flat = 2 * kH1 + kH2 * kH1 + kH2, kRest = kW3Flat + SC, kPer = (kRest + NT - 1) / NT;
+            float me[kPer], ve[kPer], pe[kPer], ge[kPer];
+            int le[kPer];
+            unsigned ee[kPer];  // (unsigned: a 32-bit offset from the uniform base pointer)
+            int t_ = tid;  // opaque: the offsets are recomputed per iteration, not kept (and spilled) across the chunks
+            asm volatile("" : "+v"(t_));
+#pragma unroll
+            for (int j = 0; j < kPer; ++j) {
+                const int i = t_ + j * NT < kRest ? t_ + j * NT : 0;
+                ee[j] = (unsigned)(i < kW3Flat ? i : i + kW3);
+                le[j] = lds_index((int)ee[j]);
+                me[j] = adam_m[ee[j]];
+                ve[j] = adam_v[ee[j]];
+                pe[j] = p[le[j]];
+                ge[j] = g[i < kW3Flat ? le[j] : le[j] - kW3];  // (db3 follows db2 in g[])
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < kPer; ++j)
+                if (t_ + j * NT < kRest) {
+                    adam1(pe[j], me[j], ve[j], ge[j], beta1, beta2, eps, step_size, inv_sqrt_bc2);
+                    p[le[j]] = pe[j];
+                    adam_m[ee[j]] = me[j];
+                    adam_v[ee[j]] = ve[j];
+                }
+            apply_dw3_from_regs(p, L, dw3, adam_m, adam_v, beta1, beta2, eps, step_size, inv_sqrt_bc2);
         } else {  // moments in global memory, element e of the flat (torch-order) vectors: coalesced; the same adam1 per element
             constexpr int kPer = 4;  // elements whose loads are in flight together
             for (int e0 = tid; e0 < L.Pflat; e0 += kPer * NT) {

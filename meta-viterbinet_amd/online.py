@@ -184,9 +184,10 @@ class OnlineTrainer:
         labels: int32 [T], the trellis states of tx when the caller already has them (kernel route only); None: calculate_states(tx)."""
         p = self.params
         dev = p[0].device
-        # the one-launch kernel keeps parameters, gradient and a chunk's activations in LDS: n_states <= 128 (up to 32 with both
-        # moments beside them; 64 / 128: the moments stay in global memory)
-        if p[5].numel() > 128 or not self.use_kernel:
+        # the one-launch kernel keeps parameters, gradient and a chunk's activations in LDS: n_states <= 256 (up to 32 with both
+        # moments beside them; 64 / 128: the moments stay in global memory; 256: W3's gradient stays in registers as well).  A CPU
+        # detector of 256 states keeps the autograd route it has always had
+        if not self.use_kernel or p[5].numel() > 256 or (p[5].numel() > 128 and not p[0].is_cuda):
             return self._online_training_autograd(tx, rx, iterations, batch_idx, full_word, return_loss)
         _lib.require_gpu_tensor(rx, "rx")
         _lib.require_gpu_tensor(p[0], "detector parameters")
@@ -222,8 +223,9 @@ class OnlineTrainer:
         return loss
 
     def words_kernel_route(self) -> bool:
-        """Does a train_words call run mvn_vnet_train_words_f32?  (A CUDA detector of at most 128 states with use_kernel.)"""
-        return bool(self.use_kernel and self.params[0].is_cuda and self.params[5].numel() <= 128)
+        """Does a train_words call run the word-axis kernel (mvn_vnet_train_words_f32; at 256 states its twin for every state count,
+        mvn_vnet_train_words_states_f32)?  (A CUDA detector of at most 256 states with use_kernel.)"""
+        return bool(self.use_kernel and self.params[0].is_cuda and self.params[5].numel() <= 256)
 
     def train_words(self, tx_words: torch.Tensor, rx_words: torch.Tensor, batch_idx: torch.Tensor = None, full_word: bool = False,
                     return_loss: bool = False, labels: torch.Tensor = None):
@@ -234,7 +236,7 @@ class OnlineTrainer:
         full_word=False: batch_idx [n, M] positions in [0, K), or drawn by select_batches(K, n); full_word=True (the whole word,
         metavnet_trainer.py:41-50) needs K == T.
         labels: int32 [n, K], the trellis states of tx_words when the caller already has them; None: calculate_states(tx_words).
-        More than 128 states, use_kernel=False and a CPU detector take stock autograd on the same state (words_kernel_route says which).
+        More than 256 states, use_kernel=False and a CPU detector take stock autograd on the same state (words_kernel_route says which).
         Returns the n losses if return_loss."""
         if tx_words.dim() != 2 or rx_words.dim() != 2 or tx_words.shape[0] != rx_words.shape[0]:
             raise ValueError("tx_words [n, K] and rx_words [n, T]")
@@ -280,19 +282,21 @@ class OnlineTrainer:
                 raise ValueError("ViterbiNet parameters must be contiguous fp32")
         loss = torch.empty(n_iter, dtype=torch.float32, device=dev) if return_loss else None
         b1, b2, eps = self.kernel_optimizer_args()
+        # (mvn_vnet_train_words_f32 stops at 128 states; the _states_ entry point is the same call up to 256)
+        name = "mvn_vnet_train_words_f32" if p[5].numel() <= 128 else "mvn_vnet_train_words_states_f32"
         with torch.cuda.device(dev):
-            rc = _lib.load().mvn_vnet_train_words_f32(_lib.ptr(y), T, _lib.ptr(labels), K, n, K, _lib.ptr(woi), _lib.ptr(idx), M, n_iter,
+            rc = getattr(_lib.load(), name)(_lib.ptr(y), T, _lib.ptr(labels), K, n, K, _lib.ptr(woi), _lib.ptr(idx), M, n_iter,
                                                       *[_lib.ptr(t.data) for t in p], _lib.ptr(self.exp_avg),
                                                       _lib.ptr(self.exp_avg_sq), self.step, self.lr, b1, b2, eps, _lib.ptr(loss),
                                                       p[5].numel(), _lib.current_stream(dev))
-        _lib.check(rc, "mvn_vnet_train_words_f32")
+        _lib.check(rc, name)
         self.step += n_iter
         return loss
 
     def _online_training_autograd(self, tx, rx, iterations, batch_idx, full_word, return_loss, word_of_iter=None, labels=None):
         """The same loop on stock PyTorch autograd (run_train_loop, trainer.py:492-505: forward 'train', CrossEntropy over the
-        selected samples, backward, Adam on the shared exp_avg / exp_avg_sq / step): the route for memory_length 8 (256 states), whose
-        parameter set does not fit the training kernel's LDS image, and for use_kernel=False.  Same draws as the kernel path (select_batches).
+        selected samples, backward, Adam on the shared exp_avg / exp_avg_sq / step): the route for use_kernel=False, for a CPU detector
+        of 256 states (memory_length 8) and for state counts above 256.  Same draws as the kernel path (select_batches).
         word_of_iter (train_words): tx [n, K] / rx [n, T] hold a word per row and iteration `it` trains on row word_of_iter[it], its
         loss over the first K positions (batch_idx then is given, or full_word); None: the one word of online_training."""
         import torch.nn.functional as F
