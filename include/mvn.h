@@ -14,6 +14,18 @@
  *     buffers and row strides that are multiples of 4 get the vector load/store paths;
  *   - calls enqueue work on `stream` (a hipStream_t; NULL = default stream) and return
  *     immediately: they never allocate, free or synchronise, so they can be graph-captured;
+ *   - what a capture FREEZES: a captured call replays the launches it issued with the arguments it issued them with.  Device
+ *     buffers are read anew by every replay (samples, weights, priors, optimizer moments, device-side descriptors such as the
+ *     trial entry points' b1pow / b2pow); everything the HOST worked out at capture time is not:
+ *       . host scalars passed by value: step counts (step0) and the powers of beta1 / beta2 the training entry points derive
+ *         from them (an Adam replay repeats the bias correction of the captured step0; SGD and RMSprop steps do not depend
+ *         on it), seeds and word0 of the Monte-Carlo and word-generator calls (a replay draws the same words again), lr, snr;
+ *       . the MVN_* switches as they stood at capture (mvn_reload_switches has no effect on a captured graph);
+ *       . the choice of kernel, made from B, T, S, pointer alignment, workspace size and the device's CU count.
+ *     A workspace (and its status word) belongs to one call at a time: a captured call's workspace must not be shared with
+ *     work that may run concurrently with a replay, other replays of the same graph included.  Under capture the calls that
+ *     use the dealt 16-state kernel put one memset node (the hand-off lines) in front of the kernel; outside capture they
+ *     issue the kernel alone;
  *   - return value: 0 = ok, <0 = bad argument (MVN_E_*), >0 = hipError_t of the failed launch.
  *   - decisions are written as fp32 {0.,1.} like the reference's decoded_word
  *     (va_detector.py:90-93); columns >= T of `dec` are not touched (caller zero-fills).
@@ -155,9 +167,12 @@ int mvn_vnet_logits_f32(const float *y, const float *W1, const float *b1, const 
  *  - Two-kernel route (S = 2; S = 256; every other S != 16 below the batch size from which the fused kernel is the faster
  *    route -- about 6 blocks per CU at 4 ... 64 states, 14 at 128; MVN_UNFUSED=1): the logits of the batch; any size that
  *    holds at least one block (T*S*4 bytes) is accepted and processed in slices.
- *  - S = 16, more than 768 blocks: at most 100 KB of hand-off lines for the dealt kernel (vnet16_dealt_kernel: the batch's
- *    32-symbol units shared evenly by 3 workgroups per CU, a block's 16 path metrics handed from wave to wave); 128-byte
- *    aligned, contents irrelevant before and after, not to be shared by calls that may run concurrently.  Without it
+ *  - S = 16, more than 768 blocks: the hand-off lines of the dealt kernel (vnet16_dealt_kernel: the batch's 32-symbol units
+ *    shared evenly by 3 workgroups per CU, a block's 16 path metrics handed from wave to wave): one 128-byte line per ring
+ *    and one for the status word, (3 x CUs + 1) x 128 B with rings of 8 waves up to (8 x 3 x CUs + 1) x 128 B with rings of
+ *    one (from 8 x 3 x CUs blocks on: 768 KB at 256 CUs); 128-byte aligned, contents irrelevant before and after -- a flag
+ *    counts as set only when it holds a number drawn for that launch, and a graph-captured call, whose number is frozen,
+ *    clears the lines itself -- not to be shared by calls that may run concurrently.  Without it
  *    (NULL / smaller / unaligned) the one-wave-per-block kernel runs: same bits, 4 % slower at 10 000 x 1000 and up to 2 x at
  *    a thousand blocks.  Word 0 of the workspace is a status word: non-zero after the call only if a hand-off wait was
  *    abandoned (the lower-numbered workgroup it waits for did not publish within seconds; the affected decisions are NaN).
@@ -700,6 +715,8 @@ int mvn_va_montecarlo_f32(const double *h, int64_t Bh, double sigma, uint64_t se
  *   `stream` without a synchronisation.  stop_frame_errors = F > 0: a round runs only if counters[2] < F held when the round before
  *   it had completed (before the first one: with the counters as passed) -- a one-thread gate kernel between the rounds decides, so
  *   a round runs whole or not at all and the same arguments give the same integers every time.  F = 0 runs every round.
+ *   (In a replayed graph the rule sees what earlier replays left in `counters`: zero them between replays for the eager call's
+ *   integers; `progress` must be zeroed before every replay, e.g. by a memset captured in front of the call.)
  *   h [Bh,L] float64 taps (row w % Bh for word w), sigma = 10^(-snr/20); W1..b3: ViterbiNet's six arrays as in mvn_vnet_decode_f32;
  *   counters: device int64[4], accumulated into; progress: device int32[2] that the caller has ZEROED, {rounds that ran, gate flag},
  *   required when n_rounds > 1 or F > 0 and otherwise optional (NULL with n_rounds = 1, F = 0: exactly one launch).

@@ -745,6 +745,17 @@ unsigned long long dealt_nonce() {
     z ^= z >> 31;
     return z ? z : 1;
 }
+// A captured launch is the exception: the graph keeps the nonce it was captured with, so a replay would find the flags its
+// previous execution SET and a waiting ring could take THAT execution's path metrics.  Under capture (and only there: an eager
+// call issues what it always did) a memset node clears the hand-off lines 1 ... n_rings ahead of the kernel, as the training
+// launchers do for their GroupSync; line 0, the status word, is the kernel's to clear.
+int dealt_clear_lines_if_capturing(void *workspace, int n_rings, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipError_t e = hipStreamIsCapturing(st, &cs); e != hipSuccess) return (int)e;
+    if (cs == hipStreamCaptureStatusNone) return 0;
+    return (int)hipMemsetAsync(static_cast<char *>(workspace) + kDealtLineFloats * sizeof(float), 0,
+                               (size_t)n_rings * kDealtLineFloats * sizeof(float), st);
+}
 // Workgroups ("groups" of 8 waves, 3 per CU) and ring size of a dealt launch.  A ring -- `ring` consecutive waves of a group --
 // owns one contiguous range of the launch's units, which must hold at least one block: the more blocks, the smaller the rings
 // (8 x groups blocks: every wave a ring of its own, the path metrics stay in its registers except at the two ends of its range;
@@ -795,7 +806,8 @@ int launch_vnet16_fused(const float *y, int64_t y_ld, const float *W1, const flo
     }
     if (can_deal) {
         const DealtPlan dp = dplan;
-        const unsigned long long nonce = dealt_nonce();  // what a SET hand-off flag holds in this launch: nothing to clear
+        const unsigned long long nonce = dealt_nonce();  // what a SET hand-off flag holds in this launch: nothing to clear ...
+        if (int e = dealt_clear_lines_if_capturing(workspace, dp.rings(), st)) return e;  // ... unless a graph will replay it
 #ifndef MVN_DIAG_PHASES  // (the phase counters live in the general form)
         if (dp.ring == 1 && !logits_out) {  // every wave a ring of its own: the form with the block loop inside
             if (tx)
@@ -1555,6 +1567,7 @@ int launch_vnet16_dealt_surv(const float *y, int64_t y_ld, const float *W1, cons
     if (unfused_forced() || (T & 3) || (reinterpret_cast<uintptr_t>(surv) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 127)) return -1;
     const DealtPlan dp = dealt_plan(B, T, false);
     if (!dp.groups || workspace_bytes < dealt_workspace_bytes(dp.rings())) return -1;
+    if (int e = dealt_clear_lines_if_capturing(workspace, dp.rings(), st)) return e;
     hipLaunchKernelGGL((vnet16_dealt_kernel<false, true>), dim3((unsigned)dp.groups), dim3(64 * kDealtWaves), 0, st, y, y_ld, W1, b1, W2, b2,
                        W3, b3, dec, dec_ld, (float *)nullptr, final_metric, (int)B, T, (const float *)nullptr, (int64_t)0, 0,
                        (const unsigned char *)nullptr, (unsigned long long *)nullptr, (float *)workspace, dp.groups, dp.ring, dealt_spin_limit(),
@@ -1677,7 +1690,7 @@ int mvn_vnet_logits_f32(const float *y, const float *W1, const float *b1, const 
 
 size_t mvn_vnet_workspace_bytes(int64_t B, int32_t T, int32_t S) {
     if (B <= 0 || T <= 0 || S <= 0) return 0;
-    if (S == 16 && !unfused_forced()) return dealt_workspace_bytes_for(B, T);  // hand-off lines of the dealt kernel (<= 100 KB), or 0
+    if (S == 16 && !unfused_forced()) return dealt_workspace_bytes_for(B, T);  // hand-off lines of the dealt kernel (a 128-byte line per ring + 1), or 0
     if (fused_ip_selected(S, B)) return 0;  // the fused kernels keep the logits on chip
     return (size_t)B * (size_t)T * (size_t)S * sizeof(float);
 }

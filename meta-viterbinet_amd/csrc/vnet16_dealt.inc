@@ -34,6 +34,7 @@ constexpr int kDealtLineFloats = 32;        // one 128-byte line per group in th
                                             // carry of bit errors, 18-19 / 20-21 the 64-bit flags of the metrics / of the carry.  A flag is
                                             // SET when it holds the launch's nonce (a fresh 64-bit number per launch, mvn_hip.hip):
                                             // nothing has to be cleared between launches, whatever the workspace held before
+                                            // (a graph-captured launch replays with ONE nonce: its launcher clears the lines, mvn_hip.hip)
 constexpr unsigned kDealtSpinLimit = 1u << 21;  // x ~2 us per poll
 
 // bytes of workspace a dealt launch of n_rings rings needs: line 0 = {status}, line 1 + r = ring r's hand-off to ring r + 1

@@ -182,7 +182,7 @@ def _vnet_val(y: torch.Tensor, params, n_states: int, T: int, return_logits: boo
     if logits is None:
         ws_bytes = int(lib.mvn_vnet_workspace_bytes(B, T, n_states))
         if ws_bytes:  # 0: a fused kernel that needs no scratch
-            if n_states != 16:  # the two-kernel route's logits, in slices of at most _WORKSPACE_CAP (16 states: <= 100 KB of hand-off lines)
+            if n_states != 16:  # the two-kernel route's logits, in slices of at most _WORKSPACE_CAP (16 states: hand-off lines, under 800 KB)
                 ws_bytes = max(min(ws_bytes, _WORKSPACE_CAP), T * n_states * 4)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=yc.device)
     with _lib.on_device(yc.device):
