@@ -64,7 +64,7 @@ typedef void *mvn_stream_t; /* hipStream_t */
 
 #define MVN_E_BARRIER (-7)   /* (status words only) a training launch abandoned its device-wide barrier */
 
-#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32, the list steps, mvn_vnet_byword_step_states_f32, mvn_vnet_byword_step_max_symbols, mvn_vnet_byword_step_states_list_f32, mvn_vnet_byword_step_list_max_symbols, mvn_va_byword_step_states_f32, mvn_va_byword_step_states_path_f32, mvn_va_byword_step_states_list_f32, mvn_va_byword_step_max_symbols, mvn_va_byword_step_list_max_symbols) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
+#define MVN_ABI_VERSION 6 /* (6, added without a bump: mvn_vnet_byword_step_path_f32, mvn_va_byword_step_path_f32, the list steps, mvn_vnet_byword_step_states_f32, mvn_vnet_byword_step_max_symbols, mvn_vnet_byword_step_states_list_f32, mvn_vnet_byword_step_list_max_symbols, mvn_va_byword_step_states_f32, mvn_va_byword_step_states_path_f32, mvn_va_byword_step_states_list_f32, mvn_va_byword_step_max_symbols, mvn_va_byword_step_list_max_symbols, the four mvn_{vnet,va}_byword_step_256[_path]_f32 with their _max_symbols and _segment) 6: workspace arguments on mvn_vnet_decode_count_f32 (the dealt 16-state kernel's hand-off lines), + the survivor / traceback entry points (incl. mvn_vnet_decode_surv_f32) and mvn_va_montecarlo_f32; 5: + mvn_vnet_train_kernel_name, mvn_va_byword_step_f32; 4: + trial-batched training / by-word step, status words; 3: training with a workspace; 2: kernel-name queries */
 
 /* ABI version of the loaded library (== MVN_ABI_VERSION). */
 int mvn_version(void);
@@ -651,6 +651,52 @@ int mvn_va_byword_step_states_list_f32(const float *rx, int64_t rx_ld, const flo
                                        float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
                                        int32_t T, int32_t nsym, int32_t pilot, int32_t S, int32_t list_bytes, float *delta,
                                        int64_t delta_ld, int32_t *choice, mvn_stream_t stream);
+
+/*
+ * The running and the path step of BOTH detectors at S = 256 states (channel memory 8), the one state count of the reference's trainer
+ * that the calls above turn down.  Same arguments, same outputs and same definitions as mvn_vnet_byword_step_states_f32 /
+ * mvn_vnet_byword_step_states_path_f32 and mvn_va_byword_step_states_f32 / mvn_va_byword_step_states_path_f32: one launch, a workgroup
+ * per word, word r with its own weights (w_stride) or row r % Bp of state_priors [Bp, 256]; labels are calculate_states with memory
+ * length 8.  Bit-identical on a data step:
+ *   running  dec to mvn_vnet_decode_f32 / mvn_va_decode_f32 (the logits are mvn_vnet_logits_f32's);
+ *   path     dec to mvn_vnet_logits_f32 / the costs above -> the survivor sweep -> mvn_traceback_f32;
+ *   all      msg, nerr, enc, label_word and labels to mvn_rs_decode_bits_f32 / mvn_rs_encode_bits_f32 and the label rule on them.
+ * A whole word [T][256] does not fit the LDS next to ViterbiNet's third layer, so the word passes through it in SEGMENTS of
+ * mvn_vnet_byword_step_256_segment() = 80 / mvn_va_byword_step_256_segment() = 128 symbols: the workgroup fills a segment, one
+ * wavefront sweeps it with the path metrics kept in registers, then the next segment is filled.  The path step keeps 16 bytes of
+ * survivors per stage for the whole word.  So the longest word is the codec's:
+ *   T <= mvn_vnet_byword_step_256_max_symbols() = mvn_va_byword_step_256_max_symbols() = 1024.
+ * There is no list step at 256 states.  The check, in the order of the steps above: S != 256 -> MVN_E_STATES; R < 0, T not a multiple
+ * of 8, T / 8 <= nsym, nsym outside 1 .. 8 or T > 1024 -> MVN_E_DIMS; a leading dimension too small -> MVN_E_DIMS; (VA) Bp < 1 ->
+ * MVN_E_PRIORS; R = 0 -> MVN_OK before any pointer is looked at; a required pointer NULL -> MVN_E_NULL (rx and state_priors may be
+ * NULL on a pilot step).  A pilot step detects nothing; the path step's pilot is the running step's.
+ * mvn_{vnet,va}_byword_step_states[_path|_list]_f32 keep answering MVN_E_STATES for S = 256, and
+ * mvn_{vnet,va}_byword_step[_list]_max_symbols(256) stay 0.  Non-finite logits, priors or received values: torch.min's /
+ * torch.argmin's rules, as at the other state counts (always: no fast path, no guard launch).
+ * (Added without a bump of MVN_ABI_VERSION, like the other steps.)
+ */
+int32_t mvn_vnet_byword_step_256_max_symbols(void);
+int32_t mvn_va_byword_step_256_max_symbols(void);
+int32_t mvn_vnet_byword_step_256_segment(void);
+int32_t mvn_va_byword_step_256_segment(void);
+int mvn_vnet_byword_step_256_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                 const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                 float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                 float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                 int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+int mvn_vnet_byword_step_256_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                      const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                      float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                      float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                      int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+int mvn_va_byword_step_256_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                               float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                               float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                               int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
+int mvn_va_byword_step_256_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                    float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                    float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                    int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream);
 
 /* The MVN_* environment switches (A/B variants of the kernels) are read once per process; a caller that
  * changes them afterwards (the test-suite does) calls this to have them read again. */

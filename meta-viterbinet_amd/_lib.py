@@ -85,6 +85,14 @@ SIGNATURES = {
     "mvn_va_byword_step_states_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_va_byword_step_states_path_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
     "mvn_va_byword_step_states_list_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + _STEP_LIST + [_vp]),
+    "mvn_vnet_byword_step_256_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_vnet_byword_step_256_path_f32": (ctypes.c_int, _STEP_VNET + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_va_byword_step_256_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_va_byword_step_256_path_f32": (ctypes.c_int, _STEP_VA + _STEP_OUT + _STEP_SCALARS + [_vp]),
+    "mvn_vnet_byword_step_256_max_symbols": (_i32, []),
+    "mvn_va_byword_step_256_max_symbols": (_i32, []),
+    "mvn_vnet_byword_step_256_segment": (_i32, []),
+    "mvn_va_byword_step_256_segment": (_i32, []),
     "mvn_reload_switches": (None, []),
     "mvn_isi_awgn_transmit": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, ctypes.c_double, _vp, _i64, _i64,
                                              _i32, _i32, _vp]),
@@ -205,6 +213,22 @@ def va_list_max_symbols(n_states: int) -> int:
     return int(load().mvn_va_byword_step_list_max_symbols(n_states))
 
 
+def step256_max_symbols() -> int:
+    """The longest word the ViterbiNet running and path steps serve at 256 states (mvn_vnet_byword_step_256_max_symbols)."""
+    return int(load().mvn_vnet_byword_step_256_max_symbols())
+
+
+def va_step256_max_symbols() -> int:
+    """The longest word the classical detector's running and path steps serve at 256 states (mvn_va_byword_step_256_max_symbols)."""
+    return int(load().mvn_va_byword_step_256_max_symbols())
+
+
+def step256_segment(kind: str = "vnet") -> int:
+    """The symbols of one LDS segment of the 256-state steps of `kind` ('vnet' / 'va'): a longer word goes through the LDS in pieces of
+    this length (mvn_{vnet,va}_byword_step_256_segment)."""
+    return int(getattr(load(), "mvn_%s_byword_step_256_segment" % kind)())
+
+
 class BywordStep:
     """One of the by-word block steps of include/mvn.h, mvn_{kind}_byword_step[_path|_list]_f32 (kind 'vnet' / 'va', decision
     'running' / 'path' / 'list'), for words of T symbols with nsym parity bytes (list: list_bytes least reliable bytes): the symbol
@@ -213,11 +237,14 @@ class BywordStep:
     harness._block_step and trials._cohort_steps pass) mvn_vnet_byword_step_states_path_f32 for decision 'path'; with
     states_list=True (what they pass as well) mvn_vnet_byword_step_states_list_f32 for kind 'vnet', decision 'list' at the state
     counts of STEP_STATES; with states_va=True (what harness._block_step and ecc.list_decode pass) kind 'va' at those state counts
-    resolves to mvn_va_byword_step_states[_path|_list]_f32; ValueError else."""
+    resolves to mvn_va_byword_step_states[_path|_list]_f32; with states_256=True (what harness._block_step passes) n_states == 256
+    with decision 'running' / 'path' resolves to mvn_{kind}_byword_step_256[_path]_f32; ValueError else."""
     def __init__(self, kind: str, decision: str, T: int, nsym: int, list_bytes=None, n_states: int = 16, states_path: bool = False,
-                 states_list: bool = False, states_va: bool = False):
+                 states_list: bool = False, states_va: bool = False, states_256: bool = False):
         self.name = "mvn_%s_byword_step%s_f32" % (kind, {"running": "", "path": "_path", "list": "_list"}[decision])
-        if states_va and kind == "va" and n_states in STEP_STATES:
+        if states_256 and n_states == 256 and kind in ("vnet", "va") and decision in ("running", "path"):
+            self.name = "mvn_%s_byword_step_256%s_f32" % (kind, "_path" if decision == "path" else "")
+        elif states_va and kind == "va" and n_states in STEP_STATES:
             self.name = "mvn_va_byword_step_states%s_f32" % {"running": "", "path": "_path", "list": "_list"}[decision]
         elif states_list and kind == "vnet" and decision == "list" and n_states in STEP_STATES:
             self.name = "mvn_vnet_byword_step_states_list_f32"

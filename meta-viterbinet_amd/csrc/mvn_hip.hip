@@ -20,6 +20,7 @@
 //   byword_step.inc, byword_step_states.inc  one block step of the by-word evaluation in one launch (16 states; 4 ... 128 states)
 //   byword_list_states.inc                 that step with the list decode at 4 ... 128 states
 //   byword_step_states_va.inc              the three steps for the classical Viterbi detector at 4 ... 128 states
+//   byword_step_256.inc                    the running and the path step of both detectors at 256 states, the word in segments
 //   online_train.inc, maml_train.inc       one-launch online training and MAML meta-learning steps
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -475,6 +476,7 @@ int ensure_dynamic_lds(const void *fn, size_t bytes);  // raises a kernel's dyna
 #include "byword_step_states.inc"
 #include "byword_list_states.inc"
 #include "byword_step_states_va.inc"
+#include "byword_step_256.inc"
 #include "online_train.inc"
 #include "maml_train.inc"
 #include "train_groups.inc"
@@ -1328,14 +1330,17 @@ int va_states_list_step_max_symbols(int32_t S) {
 // byword_step_states.inc, whose state counts and longest word are states_step_max_symbols', and the list step of
 // byword_list_states.inc, whose longest word is states_list_step_max_symbols' (a pilot's too: the list's limits come first); for the
 // classical detector the steps of byword_step_states_va.inc and va_states_step_max_symbols' / va_states_list_step_max_symbols'.
-int step_check(StepCall &c, StepDecision decision, StepDetector detector, bool any_states = false) {
+// states_256: the running and path steps of byword_step_256.inc, which serve 256 states alone, up to kStep256MaxT symbols.
+int step_check(StepCall &c, StepDecision decision, StepDetector detector, bool any_states = false, bool states_256 = false) {
     const StepOut &o = c.out;
     const int T = c.T, nsym = c.nsym;
     const bool va = detector == kStepVa;
-    const int max_T = !any_states ? kCoopMaxT
+    if (states_256 && c.S != kStep256States) return MVN_E_STATES;
+    const int max_T = states_256 ? kStep256MaxT
+                      : !any_states ? kCoopMaxT
                       : decision == kStepList ? (va ? va_states_list_step_max_symbols(c.S) : states_list_step_max_symbols(c.S))
                                               : (va ? va_states_step_max_symbols(c.S) : states_step_max_symbols(c.S));
-    if (any_states ? max_T == 0 : c.S != 16) return MVN_E_STATES;  // (the six steps of byword_step.inc exist for the 16-state detectors)
+    if (states_256 ? false : any_states ? max_T == 0 : c.S != 16) return MVN_E_STATES;  // (the six steps of byword_step.inc exist for the 16-state detectors)
     if (c.R < 0 || T < 8 || (T & 7) || T > max_T || nsym < 1 || nsym > 8 || T / 8 <= nsym) return MVN_E_DIMS;
     if (decision == kStepList) {
         c.list.ncand = list_step_candidates(T, nsym, c.list.m);
@@ -1464,6 +1469,40 @@ int va_states_step_run(StepCall c, StepDecision decision) {
     const auto head = std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.priors, c.Bp, c.dec, c.dec_ld, o.msg, o.msg_ld, o.enc, o.enc_ld,
                                       o.label_word, o.lw_ld, o.labels, o.lab_ld, o.nerr);
     return dispatch_step_states(c.S, MVN_E_STATES, [&](auto sc) { return va_states_step_launch<decltype(sc)::value>(c, decision, head); });
+}
+
+// mvn_vnet_byword_step_256_f32 / mvn_vnet_byword_step_256_path_f32 / mvn_va_byword_step_256_f32 / mvn_va_byword_step_256_path_f32:
+// one launch of a kernel of byword_step_256.inc, R workgroups of kStatesWaves waves; the dynamic LDS is one segment of the image (a
+// data step's) and, for the path, the word's survivors
+int step256_run(StepCall c, StepDecision decision, StepDetector detector) {
+    const int e = step_check(c, decision, detector, false, true);
+    if (e != MVN_OK || c.R == 0) return e;
+    if (c.pilot) decision = kStepRunning;  // (the path kernels are data steps)
+    const StepOut &o = c.out;
+    const bool path = decision == kStepPath;
+    const auto outs = std::make_tuple(c.dec, c.dec_ld, o.msg, o.msg_ld, o.enc, o.enc_ld, o.label_word, o.lw_ld, o.labels, o.lab_ld,
+                                      o.nerr);
+    const auto running = std::make_tuple(c.T, c.nsym, c.pilot);
+    const auto traced = std::make_tuple(c.T, c.nsym);
+    if (detector == kStepVa) {
+        const auto head = std::tuple_cat(std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.priors, c.Bp), outs);
+        const size_t dyn = c.pilot ? 0 : step256_dynamic_lds<true>(c.T, path), dyn_max = step256_dynamic_lds<true>(kStep256MaxT, true);
+        if (path)
+            return step_launch(byword_path_step_256_va_kernel<2>, byword_path_step_256_va_kernel<8>, c, 64 * kStatesWaves, dyn, dyn_max,
+                               std::tuple_cat(head, traced));
+        return step_launch(byword_step_256_va_kernel<2>, byword_step_256_va_kernel<8>, c, 64 * kStatesWaves, dyn, dyn_max,
+                           std::tuple_cat(head, running));
+    }
+    WeightStrides ws;
+    for (int a = 0; a < 6; ++a) ws.s[a] = c.w_stride ? (long long)c.w_stride[a] : 0;
+    const auto head =
+        std::tuple_cat(std::make_tuple(c.rx, c.rx_ld, c.tx, c.tx_ld, c.W[0], c.W[1], c.W[2], c.W[3], c.W[4], c.W[5], ws), outs);
+    const size_t dyn = c.pilot ? 0 : step256_dynamic_lds<false>(c.T, path), dyn_max = step256_dynamic_lds<false>(kStep256MaxT, true);
+    if (path)
+        return step_launch(byword_path_step_256_kernel<2>, byword_path_step_256_kernel<8>, c, 64 * kStatesWaves, dyn, dyn_max,
+                           std::tuple_cat(head, traced));
+    return step_launch(byword_step_256_kernel<2>, byword_step_256_kernel<8>, c, 64 * kStatesWaves, dyn, dyn_max,
+                       std::tuple_cat(head, running));
 }
 
 }  // namespace
@@ -1963,6 +2002,50 @@ int mvn_vnet_byword_step_states_list_f32(const float *rx, int64_t rx_ld, const f
                             {delta, delta_ld, choice, list_bytes, 0}, {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S,
                             (hipStream_t)stream},
                            kStepList);
+}
+
+// ---- the same steps at 256 states (byword_step_256.inc): step256_run above
+int32_t mvn_vnet_byword_step_256_max_symbols(void) { return kStep256MaxT; }
+int32_t mvn_va_byword_step_256_max_symbols(void) { return kStep256MaxT; }
+int32_t mvn_vnet_byword_step_256_segment(void) { return step256_seg<false>(); }
+int32_t mvn_va_byword_step_256_segment(void) { return step256_seg<true>(); }
+
+int mvn_vnet_byword_step_256_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                 const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                 float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                 float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                 int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return step256_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                        {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
+                       kStepRunning, kStepVnet);
+}
+
+int mvn_vnet_byword_step_256_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *W1, const float *b1,
+                                      const float *W2, const float *b2, const float *W3, const float *b3, const int64_t *w_stride,
+                                      float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                      float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                      int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return step256_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                        {W1, b1, W2, b2, W3, b3}, w_stride, nullptr, 0, R, pilot, S, (hipStream_t)stream},
+                       kStepPath, kStepVnet);
+}
+
+int mvn_va_byword_step_256_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                               float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                               float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                               int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return step256_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                        {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                       kStepRunning, kStepVa);
+}
+
+int mvn_va_byword_step_256_path_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,
+                                    float *dec, int64_t dec_ld, float *msg, int64_t msg_ld, float *enc, int64_t enc_ld,
+                                    float *label_word, int64_t lw_ld, int32_t *labels, int64_t lab_ld, int32_t *nerr, int64_t R,
+                                    int32_t T, int32_t nsym, int32_t pilot, int32_t S, mvn_stream_t stream) {
+    return step256_run({rx, rx_ld, tx, tx_ld, dec, dec_ld, T, nsym, {msg, msg_ld, enc, enc_ld, label_word, lw_ld, labels, lab_ld, nerr}, {},
+                        {}, nullptr, state_priors, Bp, R, pilot, S, (hipStream_t)stream},
+                       kStepPath, kStepVa);
 }
 
 int mvn_va_byword_step_f32(const float *rx, int64_t rx_ld, const float *tx, int64_t tx_ld, const float *state_priors, int64_t Bp,

@@ -347,7 +347,9 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     mvn_vnet_byword_step_states_list_f32 (_states_list_step_applies: the path step's conditions and words up to
     _lib.list_max_symbols(n_states) symbols).  A VADetector at 4, 8, 32, 64 or 128 states takes mvn_va_byword_step_states_f32, _path_f32
     and _list_f32 under the 16-state VA rule (_va_states_step_applies: words up to _lib.va_step_max_symbols(n_states), for 'list'
-    _lib.va_list_max_symbols(n_states), symbols); 2 and 256 states have no list step."""
+    _lib.va_list_max_symbols(n_states), symbols); 2 and 256 states have no list step.  At 256 states either detector takes
+    mvn_{vnet,va}_byword_step_256_f32 / _256_path_f32 for 'running' and 'path' (_step256_applies: the 16-state rules, words up to
+    _lib.step256_max_symbols() / _lib.va_step256_max_symbols() symbols)."""
     import copy
 
     from .meta import GraphedMetaStep, copy_model, meta_train_loop
@@ -374,7 +376,8 @@ def eval_by_word(detector, tx: torch.Tensor, rx: torch.Tensor, snr: float, gamma
     ser_by_word = np.zeros(N)
     K = tx.shape[1]
     va_states = fused_step and _va_states_step_applies(detector, rx, n_symbols, pass_count, decision)  # a VADetector off 16 states
-    fused = va_states or (fused_step and (_fused_step_applies(detector, rx, n_symbols, pass_count, decision)
+    step256 = fused_step and _step256_applies(detector, rx, n_symbols, pass_count, decision)  # either detector at 256 states
+    fused = step256 or va_states or (fused_step and (_fused_step_applies(detector, rx, n_symbols, pass_count, decision)
                                           or (decision == "list" and _states_list_step_applies(detector, rx, n_symbols, pass_count))))
     if decision == "list":
         if not va_states:
@@ -635,6 +638,36 @@ def _va_states_step_applies(detector, rx: torch.Tensor, n_symbols: int, pass_cou
     return T <= (_lib.va_list_max_symbols(S) if decision == "list" else _lib.va_step_max_symbols(S))
 
 
+# The detector / decision pairs of the 256-state step that eval_by_word takes by default: those that measured faster than the separate
+# launches at R = 1 (profiles/states256_step_time.txt).  A pair that is False keeps its entry point and BywordStep(states_256=True).
+_STEP256_DEFAULT = {("vnet", "running"): True, ("vnet", "path"): True, ("va", "running"): True, ("va", "path"): True}
+
+
+def _step256_applies(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, decision: str = "running") -> bool:
+    """A VNETDetector or a VADetector at 256 states (channel memory 8) takes one launch per block step (mvn_vnet_byword_step_256_f32 /
+    _256_path_f32, mvn_va_byword_step_256_f32 / _256_path_f32) under the 16-state rules of _fused_step_applies: words of whole bytes
+    longer than the parity, nsym 1 ... 8; ViterbiNet: the 'val' length is the word length and no block number is passed; VA: the
+    detector's length is the word length and ONE row of state priors (the word's own with pass_count, or the table's only row); T
+    within the step's longest word (_lib.step256_max_symbols / _lib.va_step256_max_symbols).  'list' has no step at 256 states.
+    Consulted BEFORE _va_states_step_applies, _fused_step_applies, _states_list_step_applies and _list_step_bytes, which keep
+    answering for a 256-state detector what they answered before this step existed."""
+    from . import _lib
+    from .detectors import VADetector, VNETDetector
+
+    T = rx.shape[1]
+    if getattr(detector, "n_states", None) != 256 or decision not in ("running", "path"):
+        return False
+    if not (rx.is_cuda and T % 8 == 0 and T >= 8 and 1 <= n_symbols <= 8 and T // 8 > n_symbols):
+        return False
+    if isinstance(detector, VNETDetector):
+        return (_STEP256_DEFAULT["vnet", decision] and not pass_count and detector.transmission_lengths["val"] == T
+                and T <= _lib.step256_max_symbols())
+    if isinstance(detector, VADetector):
+        return (_STEP256_DEFAULT["va", decision] and detector.transmission_length == T and (pass_count or detector.val_words == 1)
+                and T <= _lib.va_step256_max_symbols())
+    return False
+
+
 def _va_states_list_conditions(detector, rx: torch.Tensor, n_symbols: int, pass_count: bool, fused_step: bool) -> None:
     """decision='list' with a VADetector at 4, 8, 32, 64 or 128 states that _va_states_step_applies turned down: the ValueError that
     names the condition (there is no other route to fall back to).  Every other detector: nothing (_list_step_bytes speaks for it)."""
@@ -696,7 +729,7 @@ def _block_step(detector, T: int, n_symbols: int, decision: str, list_bytes):
     from .detectors import VADetector
 
     return _lib.BywordStep("va" if isinstance(detector, VADetector) else "vnet", decision, T, n_symbols, list_bytes,
-                           n_states=detector.n_states, states_path=True, states_list=True, states_va=True)
+                           n_states=detector.n_states, states_path=True, states_list=True, states_va=True, states_256=True)
 
 
 def _byword_step(step, detector, received_word: torch.Tensor, transmitted_word: torch.Tensor, pilot: bool, nerr: torch.Tensor,
